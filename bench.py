@@ -1,6 +1,6 @@
 """Headline benchmark: SCORE throughput (BASELINE.json metric, config 2).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -11,10 +11,20 @@ pass of the SCORE kernel over the GPU's 10M resident documents (inputs already
 in HBM).  Documents shard across ranks with no collective (weak scaling);
 value = documents scored by all ranks / max-over-ranks time.
 
-Also reported: the SCORE kernel's roofline position (algorithmic bytes / HIP
-event time on the launch stream) and a CPU baseline (the oracle's C
-restatement, multithreaded, on a bounded sample; kind "port" -- the Scala
-reference cannot run without a JVM).
+A plain run sets up, warms up, times the steps and prints the line; its
+roofline position (algorithmic bytes / HIP event time on the launch stream)
+comes from the timed steps themselves.  Everything that takes runs of its own
+is behind --full: the CPU baseline (the oracle's C restatement, multithreaded,
+on a bounded sample; kind "port" -- the Scala reference cannot run without a
+JVM) with the label check against it, the label accuracy against the
+generator, the host-buffer path, the mask-replay / general-key paths, and in
+fit mode the untimed statistics count (roofline, windows check), the CPU
+baseline and the count parity check.  Without --full those fields are null.
+
+--dump-outputs DIR writes what the last timed step computed as DIR/*.npy
+(float32 / float64, at most 64 MB): the labels of the SCORE launch, or the
+fitted table in fit mode.  The inputs are seeded, so two builds run with the
+same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -57,11 +67,17 @@ def parse():
                     help="distinct docs generated on the host and tiled to --docs (default: every document "
                          "distinct, drawn on the GPU)")
     ap.add_argument("--train-docs", type=int, default=None, help="training docs per language for the table")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target CPU-baseline sample time")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-path", action="store_true", help="skip the host-buffer (PCIe-inclusive) measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: CPU baseline and oracle "
+                         "checks, label accuracy, host-buffer path, mask-replay / general-key paths, fit statistics")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: target CPU-baseline sample time")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-host-path", action="store_true",
+                    help="--full without the host-buffer (PCIe-inclusive) measurement")
     ap.add_argument("--no-alt-paths", action="store_true",
-                    help="skip timing the same table on the ordered mask-replay path (diagnostics library)")
+                    help="--full without timing the same table on the ordered mask-replay path (diagnostics library)")
     ap.add_argument("--empty-table", action="store_true", help="calibration: table with no keys")
     ap.add_argument("--path", choices=["product", "replay"], default="product",
                     help="replay: time the ordered mask-replay path on the same table (diagnostics library, "
@@ -96,8 +112,8 @@ def parse():
 
 def build_table(args, ls, device):
     """FIT on the GPU (the reference's LanguageDetector.fit path) -> the
-    profile table in mask form (packed arrays), plus it as a {gram: row} dict
-    when small enough for the CPU baseline."""
+    profile table in mask form (packed arrays), plus (--full) it as a
+    {gram: row} dict when small enough for the CPU baseline."""
     grams = [int(x) for x in args.grams.split(",")]
     lang = np.repeat(np.arange(args.langs, dtype=np.int32), args.train_docs)
     data, off, lang = synth.generate(ls, len(lang), 200, 2000, seed=synth.SEED_BASE + 100, doc_lang=lang)
@@ -110,7 +126,7 @@ def build_table(args, ls, device):
     counts.close()
     n = len(ko) - 1
     table = None
-    if n * args.langs <= 1_000_000:  # larger tables reach the CPU baseline as the packed arrays
+    if args.full and n * args.langs <= 1_000_000:  # larger tables reach the CPU baseline as the packed arrays
         b = kb.tobytes()
         table = {}
         for i in range(n):
@@ -466,6 +482,58 @@ def topk_table_from_counts(kb, ko, cnt, K):
             for i in np.nonzero(chosen)[0]}
 
 
+DUMP_BYTES = 60_000_000  # --dump-outputs: every file of a run together stays under 64 MB
+DUMP_SEED = 0x1d9b
+
+
+def dump_sample(n, cap):
+    """None when all n items fit in cap, else a fixed (seeded) sample of at
+    most cap distinct indices, ascending: the same for every run of a shape."""
+    if n <= cap:
+        return None
+    return np.unique(np.random.Generator(np.random.PCG64(DUMP_SEED)).integers(0, n, size=cap))
+
+
+def dump_labels(args, d_lab, rank, world):
+    """--dump-outputs, SCORE: the labels the last timed launch wrote (what a
+    caller of score_device receives), float32, one file per rank."""
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    idx = dump_sample(len(d_lab), DUMP_BYTES // (4 * world))
+    lab = d_lab if idx is None else d_lab[torch.from_numpy(idx).to(d_lab.device)]
+    name = "labels.npy" if rank == 0 else f"labels.rank{rank}.npy"
+    np.save(os.path.join(args.dump_outputs, name), lab.cpu().numpy().astype(np.float32))
+
+
+def dump_table(args, table, distinct):
+    """--dump-outputs, FIT: the last timed fit's distinct-gram count and its
+    table (fit_table_masks) as a dense [rows, languages] float64 matrix of
+    probabilities plus the rows' key bytes ([rows, longest key] float32,
+    padded with -1); a seeded sample of the rows when they exceed the cap."""
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    np.save(os.path.join(args.dump_outputs, "distinct_grams.npy"), np.array([distinct], dtype=np.float64))
+    if table is None:  # --count-only
+        return
+    kb, ko, masks, vals = table
+    kb, ko, masks = np.asarray(kb), np.asarray(ko, dtype=np.int64), np.asarray(masks, dtype=np.uint64)
+    vals = np.asarray(vals, dtype=np.float64)
+    n = len(ko) - 1
+    lens = np.diff(ko)
+    maxlen = int(lens.max()) if n else 0
+    rows = dump_sample(n, DUMP_BYTES // (8 * args.langs + 4 * maxlen + 1))
+    if rows is None:
+        rows = np.arange(n)
+    dense = np.zeros((len(rows), args.langs), dtype=np.float64)
+    for l in range(args.langs):
+        bit = (masks[rows, l // 64] >> np.uint64(l % 64)) & np.uint64(1)
+        dense[:, l] = np.where(bit != 0, vals[rows], 0.0)
+    keys = np.full((len(rows), maxlen), -1.0, dtype=np.float32)
+    for j in range(maxlen):
+        m = lens[rows] > j
+        keys[m, j] = kb[ko[rows][m] + j]
+    np.save(os.path.join(args.dump_outputs, "table_values.npy"), dense)
+    np.save(os.path.join(args.dump_outputs, "table_keys.npy"), keys)
+
+
 def fit_main(args, world, rank, local, dev, backend):
     """Config 3 (FIT): count every window of a synthetic multilingual corpus
     (docs of 1-7 KB, drawn on the GPU, resident in HBM), merge across ranks
@@ -524,18 +592,34 @@ def fit_main(args, world, rank, local, dev, backend):
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:  # the merged table is the same on every rank
+        dump_table(args, parts[-1][2], parts[-1][1])
     count_s = float(np.mean([p[0]["count_s"] for p in parts]))
     windows = sum(int(synth_windows(off, n)) for n in grams)
-    # one more count, untimed, for the table statistics: SURVEY §8d charges the
-    # corpus byte, 12 B per document (offset + language id) and 16 B per
-    # distinct (gram, language) count written
-    c = DeviceCounts(args.langs, grams, capacity_hint=1 << 22, device=local)
-    c.count_device(d_bytes.data_ptr(), n_bytes, d_off.data_ptr(), d_lang.data_ptr(), n_docs, stream.cuda_stream)
-    torch.cuda.synchronize(dev)
-    st = c.stats()
-    c.close()
-    windows_ok = st["total"] == windows   # every window counted exactly once
-    algo = n_bytes + 12 * n_docs + 16 * st["pairs"]
+    # the count's own time against the committed counter traffic; the algorithmic
+    # bytes (the corpus byte, 12 B per document (offset + language
+    # id) and 16 B per distinct (gram, language) count written) need the table
+    # statistics of one more count, untimed: --full
+    roofline = {"bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None,
+                "traffic": count_traffic(traffic_from_profiles(f"fit:bytes={n_bytes}:L={args.langs}:G={args.grams}"),
+                                         args.langs, grams),
+                "kernel": fit_count_kernels(args.langs, grams), "count_ms": round(count_s * 1e3, 3),
+                "algorithmic_bytes_per_count": None}
+    st = windows_ok = None
+    if args.full:
+        c = DeviceCounts(args.langs, grams, capacity_hint=1 << 22, device=local)
+        c.count_device(d_bytes.data_ptr(), n_bytes, d_off.data_ptr(), d_lang.data_ptr(), n_docs, stream.cuda_stream)
+        torch.cuda.synchronize(dev)
+        st = c.stats()
+        c.close()
+        windows_ok = st["total"] == windows   # every window counted exactly once
+        algo = n_bytes + 12 * n_docs + 16 * st["pairs"]
+        roofline.update(achieved=round(algo / count_s / 1e9, 3), frac=round(algo / count_s / 1e9 / HBM_PEAK_GBS, 6),
+                        algorithmic_bytes_per_count=int(algo))
+    if roofline["traffic"]:  # the counters' view: calibrated HBM bytes per count over the count time
+        tgbs = roofline["traffic"] / count_s / 1e9
+        roofline["traffic_GBps"] = round(tgbs, 1)
+        roofline["traffic_frac"] = round(tgbs / HBM_PEAK_GBS, 4)
     line = {
         "metric": "corpus bytes/sec fitted (config 3: count + merge + probability/top-K table)",
         "value": round(n_bytes * world * args.steps / elapsed, 1), "unit": "bytes/s", "n_gpus": world,
@@ -545,7 +629,7 @@ def fit_main(args, world, rank, local, dev, backend):
         "config": {"workload": f"config3: fit {n_bytes} corpus bytes per GPU, {args.langs} languages, "
                                f"grams {args.grams}, profile size {args.profile_size}",
                    "docs_per_gpu": n_docs, "corpus_bytes_per_gpu": n_bytes, "windows_per_gpu": windows,
-                   "distinct_grams": parts[-1][1], "distinct_gram_language_pairs": st["pairs"],
+                   "distinct_grams": parts[-1][1], "distinct_gram_language_pairs": st["pairs"] if st else None,
                    "table_rows": None if args.count_only else len(parts[-1][2][1]) - 1,
                    "parallelism": f"dp{world} (corpus sharded; owner-exchange merge + distributed top-K)"},
         "phases_s": {k: round(float(np.mean([p[0].get(k, 0.0) for p in parts])), 4)
@@ -555,17 +639,8 @@ def fit_main(args, world, rank, local, dev, backend):
         "count_windows_per_s": round(windows / count_s, 1),
         "count_ms_per_gib": round(count_s * 1e3 * (1 << 30) / n_bytes, 2),
         "windows_counted_exactly_once": windows_ok,
-        "roofline": {"bound": "hbm", "achieved": round(algo / count_s / 1e9, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(algo / count_s / 1e9 / HBM_PEAK_GBS, 6),
-                     "traffic": count_traffic(traffic_from_profiles(f"fit:bytes={n_bytes}:L={args.langs}:G={args.grams}"),
-                                              args.langs, grams),
-                     "kernel": fit_count_kernels(args.langs, grams), "count_ms": round(count_s * 1e3, 3),
-                     "algorithmic_bytes_per_count": int(algo)},
+        "roofline": roofline,
     }
-    if line["roofline"]["traffic"]:  # the counters' view: calibrated HBM bytes per count over the count time
-        tgbs = line["roofline"]["traffic"] / count_s / 1e9
-        line["roofline"]["traffic_GBps"] = round(tgbs, 1)
-        line["roofline"]["traffic_frac"] = round(tgbs / HBM_PEAK_GBS, 4)
     if world > 1 and args.check_merge:
         # every rank's corpus regenerated on this GPU (same seeds), counted by
         # the oracle; the merged table (the same on every rank) must equal the
@@ -588,7 +663,7 @@ def fit_main(args, world, rank, local, dev, backend):
         expect = topk_table_from_counts(kb, ko, ocnt, args.profile_size)
         line["merged_table_matches_oracle"] = bool(masks_to_table(*parts[-1][2], args.langs) == expect)
         line["merge_check"] = {"ranks": world, "global_grams": len(okeys), "table_rows": len(expect)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         data_h = d_bytes[:min(n_bytes, 256 << 20)].cpu().numpy()
         lang_h = d_lang.cpu().numpy()
         line["cpu_baseline"], n_s, expect = cpu_baseline_fit(args, grams, data_h, off, lang_h)
@@ -681,8 +756,9 @@ def main():
                                                         chunk_docs=1 << 20)
         off = d_off.cpu().numpy()
         n_bytes = int(off[-1])
-        data = d_bytes[:n_bytes].cpu().numpy()
-        plang = d_plang.cpu().numpy()
+        # host copies only for the legs that read them (CPU baseline, host path, accuracy)
+        data = d_bytes[:n_bytes].cpu().numpy() if args.full else None
+        plang = d_plang.cpu().numpy() if args.full else None
         del d_plang
     else:
         pool = min(args.pool, args.docs)
@@ -724,8 +800,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs:
+        dump_labels(args, d_lab, rank, world)
+
     # labels sanity (synthetic docs carry their generating language)
-    acc = float((d_lab[:pool].cpu().numpy() == plang[:pool]).mean()) if (table or packed) else None
+    acc = float((d_lab[:pool].cpu().numpy() == plang[:pool]).mean()) if args.full and (table or packed) else None
 
     info = model.info()
     doc_b = n_bytes / max(n_docs, 1)                      # mean document bytes
@@ -734,7 +813,7 @@ def main():
     cpu = None
     oracle_check = None
     hits = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and (table or packed):
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and (table or packed):
         cpu, ol, hits = cpu_baseline(args, table, grams, data, off, packed)
         # the timed kernel's own labels (the last step's) against the oracle's
         # on the CPU sample: the exact code path the value measures
@@ -792,13 +871,13 @@ def main():
         roofline["traffic_frac"] = round(tgbs / HBM_PEAK_GBS, 4)
 
     alt = None
-    if rank == 0 and world == 1 and args.config == 2 and not args.no_alt_paths and not args.empty_table:
+    if args.full and rank == 0 and world == 1 and args.config == 2 and not args.no_alt_paths and not args.empty_table:
         alt = mask_replay_path(args, packed, grams, local, d_bytes, n_bytes, d_off, n_docs, d_lab, stream)
     general = None
-    if rank == 0 and world == 1 and args.config == 2 and not args.no_alt_paths and table:
+    if args.full and rank == 0 and world == 1 and args.config == 2 and not args.no_alt_paths and table:
         general = general_key_path(args, table, grams, local, d_bytes, d_off, n_docs, d_lab, stream)
     host = None
-    if rank == 0 and world == 1 and not args.no_host_path and not args.empty_table:
+    if args.full and rank == 0 and world == 1 and not args.no_host_path and not args.empty_table:
         host = host_path(model, data, off, acc_labels=d_lab.cpu().numpy())
 
     total_docs = n_docs * world * args.steps

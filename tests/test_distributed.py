@@ -278,3 +278,35 @@ def test_bench_gpus2_launches_two_ranks():
     assert line["n_gpus"] == 2 and line["scaling"] == "weak"
     assert line["config"]["docs_per_gpu"] == 200000
     assert abs(line["value"] - 2 * 200000 * 3 / (line["ms_per_step"] * 3 / 1e3)) / line["value"] < 1e-3
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_its_labels(tmp_path):
+    """A plain bench.py run times its steps and nothing else (every --full
+    field is null), --steps sets the number of timed steps, and
+    --dump-outputs writes the last step's labels as float32: the same from
+    run to run (seeded inputs)."""
+    import json
+    import subprocess
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    labels = []
+    for i, steps in enumerate((2, 3)):
+        out = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps),
+                            "--warmup", "1", "--docs", "50000", "--dump-outputs", str(out)], env=env,
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
+        assert line["steps"] == steps and line["ms_per_step"] > 0 and line["unit"] == "docs/s"
+        # value is docs per second of the same steps (ms_per_step is printed to 1e-4 ms)
+        assert abs(line["value"] - 50000 / (line["ms_per_step"] / 1e3)) / line["value"] < 1e-4 / line["ms_per_step"] + 1e-6
+        for k in ("cpu_baseline", "oracle_check", "labels_match_oracle", "host_path", "mask_replay_path",
+                  "general_keys_path", "label_accuracy_vs_generator"):
+            assert line[k] is None, k
+        assert sorted(os.listdir(out)) == ["labels.npy"]
+        labels.append(np.load(out / "labels.npy"))
+    assert labels[0].dtype == np.float32 and labels[0].shape == (50000,)
+    assert 0 <= labels[0].min() and labels[0].max() < 20 and len(np.unique(labels[0])) == 20
+    assert np.array_equal(labels[0], labels[1])

@@ -156,6 +156,37 @@ def test_bench_traffic_lookup_scales_profiled_launch():
     assert bench.traffic_from_profiles(key.replace(":L=200:", ":L=201:")) is None
 
 
+def test_bench_dump_table_and_sample(tmp_path):
+    """bench.py --dump-outputs (fit mode): the packed mask table comes out as
+    a dense float64 probability matrix and float32 key bytes; a sample of a
+    larger output is ascending, within its cap and the same on every call."""
+    import argparse
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    kb = np.frombuffer(b"a" + b"th" + b"ing", dtype=np.uint8)
+    ko = np.array([0, 1, 3, 6], dtype=np.int64)
+    masks = np.zeros((3, 2), dtype=np.uint64)
+    masks[0, 0], masks[1, 1], masks[2, 0] = 0b101, 1, np.uint64(1) << np.uint64(63)
+    vals = np.array([0.5, 0.25, 0.125])
+    args = argparse.Namespace(dump_outputs=str(tmp_path / "out"), langs=65)
+    bench.dump_table(args, (kb, ko, masks, vals), 7)
+    v = np.load(tmp_path / "out" / "table_values.npy")
+    k = np.load(tmp_path / "out" / "table_keys.npy")
+    assert v.dtype == np.float64 and v.shape == (3, 65) and k.dtype == np.float32
+    want = np.zeros((3, 65))
+    want[0, 0] = want[0, 2] = 0.5
+    want[1, 64] = 0.25
+    want[2, 63] = 0.125
+    assert np.array_equal(v, want)
+    assert k.tolist() == [[97, -1, -1], [116, 104, -1], [105, 110, 103]]
+    assert np.load(tmp_path / "out" / "distinct_grams.npy").tolist() == [7.0]
+    assert bench.dump_sample(10, 10) is None
+    s = bench.dump_sample(1000, 100)
+    assert 0 < len(s) <= 100 and np.all(np.diff(s) > 0) and s[-1] < 1000
+    assert np.array_equal(s, bench.dump_sample(1000, 100))
+
+
 def test_detect_cache_reuses_only_unchanged_maps():
     """The detect() cache (api._detect_model) may reuse a device table only
     while the map's contents equal the snapshot it was built from."""

@@ -20,13 +20,13 @@ step() {  # name timeout cmd...
 ONLY=${ONLY:-c2 prof c4 c5 fit}
 for s in $ONLY; do
   case $s in
-    c2)   step bench_c2 300 python -u bench.py --json-out "$OUT/bench_c2.json" ;;
+    c2)   step bench_c2 300 python -u bench.py --full --json-out "$OUT/bench_c2.json" ;;
     prof) step rocprof_c2 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$PWD/$OUT/prof_c2" -o run \
             -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-host-path --no-alt-paths
           find "$OUT/prof_c2" -name "*kernel_stats.csv" -exec cp {} "$OUT/kernel_stats_c2.csv" \; ;;
-    c4)   step bench_c4 400 python -u bench.py --config 4 --steps 10 --warmup 2 --json-out "$OUT/bench_c4.json" ;;
-    c5)   step bench_c5 500 python -u bench.py --config 5 --steps 5 --warmup 1 --no-host-path --json-out "$OUT/bench_c5.json" ;;
-    fit)  step bench_fit 400 python -u bench.py --mode fit --steps 5 --warmup 1 --json-out "$OUT/bench_fit.json" ;;
+    c4)   step bench_c4 400 python -u bench.py --config 4 --steps 10 --warmup 2 --full --json-out "$OUT/bench_c4.json" ;;
+    c5)   step bench_c5 500 python -u bench.py --config 5 --steps 5 --warmup 1 --full --no-host-path --json-out "$OUT/bench_c5.json" ;;
+    fit)  step bench_fit 400 python -u bench.py --mode fit --steps 5 --warmup 1 --full --json-out "$OUT/bench_fit.json" ;;
   esac
 done
 echo "== done"
