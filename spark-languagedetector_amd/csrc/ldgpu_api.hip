@@ -3069,9 +3069,11 @@ int derive_pending(ldgpu_counts* c) {
 }
 
 // Partial windows of the call's documents shorter than some gram length
-// (partial_kernel): one add each, straight into T.
+// (partial_kernel): one add each, straight into T.  long_only: those of the
+// gram lengths beyond 15 bytes alone (the legacy kernels count the partial
+// windows of their own lengths).
 int count_partial(ldgpu_counts* c, const uint8_t* d_bytes, const int64_t* d_offsets, const int32_t* d_lang,
-                  int64_t n_docs, const int64_t* h_off, const int32_t* h_lang) {
+                  int64_t n_docs, const int64_t* h_off, const int32_t* h_lang, bool long_only = false) {
     int maxg = 0;
     for (int i = 0; i < c->nGall; ++i) maxg = std::max(maxg, c->Gall[i]);
     std::vector<int64_t> docs;
@@ -3079,6 +3081,7 @@ int count_partial(ldgpu_counts* c, const uint8_t* d_bytes, const int64_t* d_offs
     for (int64_t d = 0; d < n_docs; ++d) {
         const int64_t len = h_off[d + 1] - h_off[d];
         if (len <= 0 || len >= maxg || h_lang[d] < 0 || h_lang[d] >= c->L) continue;
+        if (long_only && len > kMaxWideGram) continue;  // (long_count_launch: the whole text as a long key)
         docs.push_back(d);
         any_wide |= len > kMaxGram;
     }
@@ -3095,7 +3098,7 @@ int count_partial(ldgpu_counts* c, const uint8_t* d_bytes, const int64_t* d_offs
     HIP_TRY(hipMemcpyAsync(x->f_ocnt.p, docs.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(c->d_ovf_n, 0, sizeof(unsigned int), st));
     HIP_TRY(launch_partial(d_bytes, d_offsets, d_lang, (const int64_t*)x->f_ocnt.p, n, count_params(c), wide_params(c),
-                           derive_params(c), st));
+                           long_only ? long_lengths(c) : derive_params(c), st));
     if (any_wide) {
         if (int rc = wide_after(c)) return rc;
     }
@@ -3715,6 +3718,10 @@ int count_launch(ldgpu_counts* c, const uint8_t* d_bytes, int64_t n_bytes, const
     }
     if (c->nGw > 0) {
         if (int rc = wide_count_launch(c, d_bytes, n_bytes, d_offsets, d_lang, n_docs, h_off)) return rc;
+    }
+    if (c->nGl > 0) {  // gram lengths beyond 15 bytes have no legacy kernel: their own table, as in FIT v4
+        if (int rc = count_partial(c, d_bytes, d_offsets, d_lang, n_docs, h_off, h_lang, true)) return rc;
+        if (int rc = long_count_launch(c, d_bytes, d_offsets, d_lang, n_docs, h_off, h_lang)) return rc;
     }
     return LDGPU_OK;
 }

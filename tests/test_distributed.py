@@ -33,17 +33,26 @@ def _init(rank, world, port):
     return dist
 
 
-def _corpus():
+def _corpus(kind="synth"):
+    """(languages with .names, (data, offsets, labels) in the FIT encoding, the
+    documents' texts); kind "bytes": tests/bytecorpus.py's six scripts, UTF-8."""
     from languagedetection import synth
+    if kind == "bytes":
+        import types
+        import bytecorpus
+        lang, txts = bytecorpus.texts(21, 6, 500, 0, 150)
+        data, off = bytecorpus.fit_pack(txts)
+        return types.SimpleNamespace(names=synth.language_names(6)), (data, off, lang), txts
     ls = synth.make_languages(6, seed=21)
-    return ls, synth.generate(ls, 500, 0, 300, seed=22)
+    data, off, lang = synth.generate(ls, 500, 0, 300, seed=22)
+    return ls, (data, off, lang), synth.texts(data, off)
 
 
-def _merge_worker(rank, world, port, out_dir):
+def _merge_worker(rank, world, port, out_dir, kind="synth"):
     dist = _init(rank, world, port)
     import ldoracle_c as OC
     from languagedetection.distributed import merge_counts, shard_range
-    ls, (data, off, lang) = _corpus()
+    ls, (data, off, lang), _ = _corpus(kind)
     lo, hi = shard_range(len(off) - 1, rank, world)
     sub_off = off[lo:hi + 1] - off[lo]
     sub = data[off[lo]:off[hi]]
@@ -73,19 +82,24 @@ def test_merge_counts_two_ranks(tmp_path):
     single-process counts."""
     import ldoracle_c as OC
     from languagedetection.distributed import owner_of, packed_keys
-    mp.spawn(_merge_worker, args=(2, free_port(), str(tmp_path)), nprocs=2, join=True)
-    ls, (data, off, lang) = _corpus()
-    keys, cnt = OC.count(data, off, lang, 6, [1, 2, 3])
-    got = {}
-    for r in range(2):
-        rk = _read_keys(os.path.join(tmp_path, f"keys{r}.bin"))
-        rc = np.load(os.path.join(tmp_path, f"counts{r}.npy"))
-        assert (owner_of(packed_keys(rk), 2) == r).all()
-        for k, row in zip(rk, rc):
-            assert k not in got
-            got[k] = row
-    assert sorted(got, key=lambda k: (len(k), k)) == keys
-    assert np.array_equal(np.array([got[k] for k in keys]), cnt)
+    for kind in ("synth", "bytes"):     # bytes: keys of bytes >= 0x80 and 0x00 through the owner hash
+        mp.spawn(_merge_worker, args=(2, free_port(), str(tmp_path), kind), nprocs=2, join=True)
+        ls, (data, off, lang), _ = _corpus(kind)
+        keys, cnt = OC.count(data, off, lang, 6, [1, 2, 3])
+        assert kind == "synth" or (sum(k[0] >= 0x80 for k in keys) > len(keys) // 3 and any(0 in k for k in keys))
+        got = {}
+        owned = []
+        for r in range(2):
+            rk = _read_keys(os.path.join(tmp_path, f"keys{r}.bin"))
+            rc = np.load(os.path.join(tmp_path, f"counts{r}.npy"))
+            assert (owner_of(packed_keys(rk), 2) == r).all()
+            owned.append(len(rk))
+            for k, row in zip(rk, rc):
+                assert k not in got
+                got[k] = row
+        assert min(owned) > len(keys) // 4      # the owner hash spreads these keys too
+        assert sorted(got, key=lambda k: (len(k), k)) == keys
+        assert np.array_equal(np.array([got[k] for k in keys]), cnt)
 
 
 def test_sort_keys_roundtrip_and_order():
@@ -99,13 +113,12 @@ def test_sort_keys_roundtrip_and_order():
     assert cover == [(0, 3), (3, 6), (6, 10)]
 
 
-def _fit_worker(rank, world, port, out_dir, K, grams, transport):
+def _fit_worker(rank, world, port, out_dir, K, grams, transport, kind="synth"):
     dist = _init(rank, world, port)
-    from languagedetection import synth
     from languagedetection.api import LanguageDetector
     from languagedetection.distributed import Communicator, merge_counts_device, shard_range
-    ls, (data, off, lang) = _corpus()
-    rows = list(zip([ls.names[i] for i in lang], synth.texts(data, off)))
+    ls, (data, off, lang), txts = _corpus(kind)
+    rows = list(zip([ls.names[i] for i in lang], txts))
     lo, hi = shard_range(len(rows), rank, world)
     local = LanguageDetector.count_grams(rows[lo:hi], grams, ls.names, device=0)
     comm = Communicator(device=0, transport=transport)
@@ -122,13 +135,12 @@ def _fit_worker(rank, world, port, out_dir, K, grams, transport):
     dist.destroy_process_group()
 
 
-def _check_fit(tmp_path, world, K, grams):
+def _check_fit(tmp_path, world, K, grams, kind="synth"):
     import json
     import ldoracle as O
     import ldoracle_c as OC
-    from languagedetection import synth
-    ls, (data, off, lang) = _corpus()
-    rows = list(zip([ls.names[i] for i in lang], synth.texts(data, off)))
+    ls, (data, off, lang), txts = _corpus(kind)
+    rows = list(zip([ls.names[i] for i in lang], txts))
     expect = O.filter_top_grams(O.fit_probabilities(rows, ls.names, grams), ls.names, K)
     okeys, ocnt = OC.count(data, off, lang, 6, grams)
     counts = {}
@@ -144,18 +156,23 @@ def _check_fit(tmp_path, world, K, grams):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("K,grams", [(80, [1, 2, 3]), (5000, [2, 3]), (60, [2, 9]), (5000, [1, 8, 12]),
-                                     (60, [2, 17]), (5000, [1, 16, 9])])
-def test_fit_distributed_matches_single_process(tmp_path, K, grams):
+@pytest.mark.parametrize("K,grams,kind", [
+    pytest.param(80, [1, 2, 3], "synth", id="80-grams0"), pytest.param(5000, [2, 3], "synth", id="5000-grams1"),
+    pytest.param(60, [2, 9], "synth", id="60-grams2"), pytest.param(5000, [1, 8, 12], "synth", id="5000-grams3"),
+    pytest.param(60, [2, 17], "synth", id="60-grams4"), pytest.param(5000, [1, 16, 9], "synth", id="5000-grams5"),
+    pytest.param(80, [1, 2, 3], "bytes", id="80-grams0-bytes"), pytest.param(60, [2, 9], "bytes", id="60-grams2-bytes"),
+])
+def test_fit_distributed_matches_single_process(tmp_path, K, grams, kind):
     """Two ranks (cuda:0 each), host transport over gloo: the library's owner
     exchange leaves disjoint shards with the oracle's global counts, and the
     distributed top-K gives every rank the oracle's table -- also with K above
     some language's present grams (the zero-valued fill), and with gram
     lengths 8..15 (wide grams) or beyond (long grams): every rank's entries
     all-gathered, each rank keeping those it owns; the top-K over every rank's
-    presence rows."""
-    mp.spawn(_fit_worker, args=(2, free_port(), str(tmp_path), K, grams, "host"), nprocs=2, join=True)
-    _check_fit(tmp_path, 2, K, grams)
+    presence rows.  kind "bytes": the same on UTF-8 text of six scripts (the
+    multi-rank selection on u64 keys whose first byte is >= 0x80)."""
+    mp.spawn(_fit_worker, args=(2, free_port(), str(tmp_path), K, grams, "host", kind), nprocs=2, join=True)
+    _check_fit(tmp_path, 2, K, grams, kind)
 
 
 @pytest.mark.gpu
@@ -174,7 +191,7 @@ def _fail_worker(rank, world, port, out_dir, K, grams, point):
     from languagedetection import synth
     from languagedetection.distributed import Communicator, merge_counts_device, shard_range
     from languagedetection.runtime import DeviceCounts
-    ls, (data, off, lang) = _corpus()
+    ls, (data, off, lang), _ = _corpus()
     lo, hi = shard_range(len(off) - 1, rank, world)
     local = DeviceCounts(6, grams, device=0, variant="diag")
     local.count(data[off[lo]:off[hi]], off[lo:hi + 1] - off[lo], lang[lo:hi])

@@ -8,6 +8,7 @@ import pytest
 
 import ldoracle as O
 import ldoracle_c as OC
+from bytecorpus import _sparse_topk_masks, _topk_table_from_counts
 from conftest import GOLDEN
 from languagedetection import LanguageDetector, LanguageDetectorModel, encoding, synth
 from languagedetection.runtime import DeviceCounts
@@ -215,23 +216,6 @@ def test_fit_tables_of_two_count_tables_on_one_context():
     b.close()
 
 
-def _topk_table_from_counts(keys, cnt, L, K):
-    """filterTopGrams (LanguageDetector.scala:100-132) over oracle counts,
-    vectorised: v_l = log(1 + [l] / k); per language the K largest v_l, ties
-    by ascending (length, bytes) = index order of the sorted keys."""
-    pres = cnt > 0
-    k = pres.sum(axis=1)
-    w = np.zeros(len(keys))
-    w[k > 0] = np.log(1.0 + 1.0 / k[k > 0])
-    chosen = np.zeros(len(keys), dtype=bool)
-    idx = np.arange(len(keys))
-    for l in range(L):
-        v = np.where(pres[:, l], w, 0.0)
-        order = np.lexsort((idx, -v))
-        chosen[order[:K]] = True
-    return {keys[i]: [float(w[i]) if pres[i, l] else 0.0 for l in range(L)] for i in np.nonzero(chosen)[0]}
-
-
 def test_fit_and_score_more_than_256_languages():
     """L > 256: FIT counts / top-K unchanged in form (mask words ceil(L/64)),
     and the model scores in language blocks of 256 (one launch per block,
@@ -290,7 +274,8 @@ def test_config3_shape_counts_and_table():
     assert all(table[g] == expect[g] for g in expect)
 
 
-@pytest.mark.parametrize("variant,env", [
+# (library variant, diagnostics switches): every counting path
+COUNT_VARIANTS = [
     ("product", {}),                                         # FIT v4, the table's own record form: one batch
     ("diag", {"LDGPU_FIT_BATCH_WINDOWS": "20000"}),          # FIT v4: many small batches
     ("diag", {"LDGPU_FIT_K": "2"}),                          # two-word records: FIT v5 (sort + runs)
@@ -300,7 +285,10 @@ def test_config3_shape_counts_and_table():
     ("diag", {"LDGPU_FIT_K": "3", "LDGPU_FIT_BATCH_WINDOWS": "50000"}),  # three-word records, several batches
     ("diag", {"LDGPU_FIT_BATCH_WINDOWS": "700"}),            # batches of one document (most are longer)
     ("diag", {"LDGPU_FIT_LEGACY": "1"}),                     # round-1 single-pass atomic kernels (A/B only)
-])
+]
+
+
+@pytest.mark.parametrize("variant,env", COUNT_VARIANTS)
 @pytest.mark.parametrize("L,grams", [(20, [1, 2, 3, 4, 5]), (100, [1, 2, 6]), (256, [3, 1, 3]), (2, [5, 4]),
                                      (200, [1, 2, 3, 4, 5, 6, 7]), (20, [7]), (5, [2, 9, 15]), (30, [8, 1])])
 def test_count_paths_match_oracle(L, grams, variant, env, monkeypatch):
@@ -519,33 +507,6 @@ def test_bench_fit_two_ranks_merged_table_matches_oracle(tmp_path):
     assert line["n_gpus"] == 2
     assert line["merged_table_matches_oracle"] is True, line.get("merge_check")
     assert line["windows_counted_exactly_once"] is True
-
-
-def _sparse_topk_masks(expect, L, K):
-    """filterTopGrams over the oracle's sparse counts (kb, ko, po, pl, pc in
-    (length, bytes, language) order): every gram in some language's top K by
-    (v_l desc, index asc), as (keys, mask words [n][ceil(L/64)], values)."""
-    kb, ko, po, pl, pc = expect
-    n = len(ko) - 1
-    k = np.diff(po)
-    w = np.zeros(n)
-    w[k > 0] = np.log(1.0 + 1.0 / k[k > 0])
-    g = np.repeat(np.arange(n), k)
-    order = np.lexsort((g, -w[g], pl))
-    sl = pl[order]
-    chosen = np.zeros(n, dtype=bool)
-    starts = np.searchsorted(sl, np.arange(L + 1))
-    for l in range(L):
-        chosen[g[order[starts[l]:min(starts[l + 1], starts[l] + K)]]] = True
-    idx = np.nonzero(chosen)[0]
-    b = kb.tobytes()
-    keys = [b[ko[i]:ko[i + 1]] for i in idx]
-    words = (L + 63) // 64
-    masks = np.zeros((len(idx), words), dtype=np.uint64)
-    for j, i in enumerate(idx):
-        for l in pl[po[i]:po[i + 1]]:
-            masks[j, l // 64] |= np.uint64(1) << np.uint64(l % 64)
-    return keys, masks, w[idx]
 
 
 def test_config5_shape_fit_counts_table_and_scores():

@@ -184,6 +184,134 @@ def test_c_oracle_mask_form_equals_dense_rows():
     assert np.array_equal(l1, l2) and np.array_equal(s1.view(np.uint64), s2.view(np.uint64))
 
 
+# ------------------------- the same on non-ASCII bytes (tests/bytecorpus.py)
+BYTE_SEED, BYTE_L = 5, 18
+
+
+@pytest.fixture(scope="module")
+def byte_corpus():
+    """18 languages (every block twice), 720 documents of up to 120 units:
+    (names, labels, texts, FIT pack)."""
+    import bytecorpus as B
+    labels, txts = B.texts(BYTE_SEED, BYTE_L, 720, 0, 120)
+    return [f"l{i:02d}" for i in range(BYTE_L)], labels, txts, B.fit_pack(txts)
+
+
+def _py_count_bytes(docs, labels, grams, into):
+    """computeGrams + reduceGrams of the Python oracle over byte documents
+    (raw_docs are not the UTF-8 of any string): O.sliding per n in order,
+    duplicates included, Int sums."""
+    for d, l in zip(docs, labels):
+        if l < 0:
+            continue
+        for n in grams:
+            for w in O.sliding(d, n):
+                into[(l, w)] = O.int32_wrap(into.get((l, w), 0) + 1)
+    return into
+
+
+@pytest.mark.parametrize("grams", [[1, 3, 2, 7, 3], [2, 9, 17]])
+def test_c_oracle_matches_python_count_on_bytes(byte_corpus, grams):
+    """Counts as a dictionary and the key order, on UTF-8 text of every block
+    (through O.fit_encode on one side, the package's encoding on the other)
+    followed by raw_docs (0x00 / 0xFF runs, random bytes), some labels -1."""
+    import bytecorpus as B
+    names, labels, txts, (data, off) = byte_corpus
+    raw = B.raw_docs(BYTE_SEED)
+    rl = np.random.default_rng(BYTE_SEED).integers(-1, BYTE_L, size=len(raw)).astype(np.int32)
+    reduced = O.reduce_grams(O.compute_grams([(names[l], t) for l, t in zip(labels, txts)], grams), names)
+    expect = {(names.index(l), g): c for (l, g), c in reduced.items()}
+    _py_count_bytes(raw, rl.tolist(), grams, expect)
+    n = int(off[-1])
+    d2, o2 = B.encoding.pack([bytes(data[:n])] + raw)
+    o2 = np.concatenate([off[:-1], o2[1:]])              # the text documents keep their own boundaries
+    keys, cnt = OC.count(d2, o2, np.concatenate([labels, rl]), BYTE_L, grams)
+    got = {(l, k): int(cnt[i, l]) for i, k in enumerate(keys) for l in range(BYTE_L) if cnt[i, l]}
+    assert got == expect
+    assert keys == sorted({g for _, g in expect}, key=O.key_order)
+    assert any(k[0] >= 0x80 for k in keys) and any(0 in k for k in keys)
+    # the threaded count and the sparse export (what the GPU tests of large L compare with) say the same
+    k2, c2 = OC.count(d2, o2, np.concatenate([labels, rl]), BYTE_L, grams, nthreads=2)
+    assert k2 == keys and np.array_equal(c2, cnt)
+    kb, ko, po, pl, pc = OC.count_sparse(d2, o2, np.concatenate([labels, rl]), BYTE_L, grams)
+    assert [kb[ko[i]:ko[i + 1]].tobytes() for i in range(len(ko) - 1)] == keys
+    rows = np.zeros_like(cnt)
+    rows[np.repeat(np.arange(len(keys)), np.diff(po)), pl] = pc
+    assert np.array_equal(rows, cnt) and (pc > 0).all()
+    assert all((np.diff(pl[po[i]:po[i + 1]]) > 0).all() for i in range(len(keys)))
+
+
+@pytest.mark.parametrize("form", ["dense", "mask"])
+def test_c_oracle_matches_python_score_on_bytes(form):
+    """Scores bit for bit and labels on score_pack(texts) interleaved with
+    raw_docs, a table with 0x00 / 0xFF keys, one and two threads."""
+    import bytecorpus as B
+    L, grams = 7, [1, 3, 2, 8, 3]
+    table = B.byte_table(BYTE_SEED, L, [1, 2, 3, 8], 500, form)
+    _, txts = B.texts(BYTE_SEED, L, 150, 0, 60)
+    docs = B.interleave([O.score_encode(t) for t in txts], B.raw_docs(BYTE_SEED))
+    data, off = B.encoding.pack(docs)
+    assert bytes(data[:int(off[-1])]) == b"".join(docs)
+    expect = [O.detect_scores(d, table, L, grams) for d in docs]
+    assert sum(any(s) for s in expect) > len(docs) // 2      # the keys are hit
+    for nthreads in (1, 2):
+        labels, scores = OC.Table(table, L).score(grams, data, off, want_scores=True, nthreads=nthreads)
+        assert scores.view(np.uint64).tolist() == np.array(expect).view(np.uint64).tolist()
+        assert labels.tolist() == [O.argmax_first(s) for s in expect]
+
+
+def test_byte_corpus_reaches_what_ascii_cannot(byte_corpus):
+    """Conditions on the inputs themselves, from the oracle: without them the
+    byte tests would pass for the reason the ASCII ones do."""
+    import bytecorpus as B
+    names, labels, txts, (data, off) = byte_corpus
+    assert [bytes(data[off[i]:off[i + 1]]) for i in range(len(txts))] == [O.fit_encode(t) for t in txts]
+    keys, cnt = OC.count(data, off, labels, BYTE_L, [1, 2, 3])
+    assert np.mean([k[0] >= 0x80 for k in keys]) >= 0.40
+    assert any(0 in k for k in keys)
+    pk = (cnt > 0).sum(axis=1)
+    assert (pk == 1).any() and (pk == 2).any() and (pk >= 3).any()
+    assert cnt.max() > 1000
+    sdata, soff = B.score_pack(txts)
+    sb = sdata[:int(soff[-1])]
+    assert bytes(sb) == b"".join(O.score_encode(t) for t in txts)
+    assert (sb == 0x00).any() and (sb == 0xFF).any()
+    assert (np.unique(sb) >= 0x80).sum() > 64        # most of the upper half, which ASCII text never has
+
+
+def test_numpy_top_k_rule_equals_oracle_filter_top_grams(byte_corpus):
+    """_topk_table_from_counts (the rule every GPU fit-table test compares
+    with) against O.filter_top_grams on the UTF-8 corpus, in the three K
+    regimes: the cut inside a tie group whose keys' first bytes straddle 0x80,
+    K between the languages' present counts (zero-valued fill), K above the
+    number of grams."""
+    import bytecorpus as B
+    names, labels, txts, (data, off) = byte_corpus
+    grams = [1, 2, 3]
+    keys, cnt = OC.count(data, off, labels, BYTE_L, grams)
+    probs = O.fit_probabilities([(names[l], t) for l, t in zip(labels, txts)], names, grams)
+    Ka, Kb, Kc, split = B.k_regimes(keys, cnt)
+    present = (cnt > 0).sum(axis=0)
+    assert split and Ka < present.min() < Kb <= present.max() and Kc > len(keys)
+    for K in (Ka, Kb, Kc):
+        assert B._topk_table_from_counts(keys, cnt, BYTE_L, K) == O.filter_top_grams(probs, names, K)
+    # what the split means: ties broken by (length, SIGNED bytes) keep other grams at Ka
+    perm = sorted(range(len(keys)), key=lambda i: (len(keys[i]), [b - 256 if b >= 128 else b for b in keys[i]]))
+    signed = B._topk_table_from_counts([keys[i] for i in perm], cnt[perm], BYTE_L, Ka)
+    assert signed.keys() != B._topk_table_from_counts(keys, cnt, BYTE_L, Ka).keys()
+    # every presence class up to 300 languages: gram i is present in languages 0..i
+    L = 300
+    keys = sorted((bytes([i % 256, i // 256]) for i in range(L)), key=O.key_order)
+    cnt = np.tril(np.ones((L, L), dtype=np.int64))
+    probs = {g: [math.log(1.0 + 1.0 / (i + 1)) if l <= i else 0.0 for l in range(L)] for i, g in enumerate(keys)}
+    assert B._topk_table_from_counts(keys, cnt, L, 7) == O.filter_top_grams(probs, [str(l) for l in range(L)], 7)
+    po = np.concatenate([[0], np.cumsum(np.arange(1, L + 1))])
+    pl = np.concatenate([np.arange(i + 1) for i in range(L)]).astype(np.int32)
+    skeys, _, vals = B._sparse_topk_masks((np.frombuffer(b"".join(keys), np.uint8), np.arange(0, 2 * L + 1, 2), po, pl,
+                                           np.ones(len(pl), np.int64)), L, L)
+    assert skeys == keys and vals.tolist() == [probs[g][0] for g in keys]
+
+
 def test_c_restatement_under_address_and_ub_sanitizers():
     """SURVEY §5 (race detection / sanitizers): the C restatement built with
     -fsanitize=address,undefined (make -C oracle asan) runs every entry point
