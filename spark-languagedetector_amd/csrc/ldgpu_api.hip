@@ -1533,7 +1533,13 @@ int model_build(ldgpu_ctx* ctx, int32_t n_langs, const int32_t* gram_lengths, in
                 for (uint32_t b = 0; b < 32; ++b)
                     if ((filter[kBmp1Words + wd] >> b) & 1u) lang2.push_back(lang2of[bmp2_unword(wd) * 32 + b]);
             }
-            const uint32_t dwords = 64u + 1024u + (uint32_t)((lang2.size() + 16) / 16) * 4u;  // uint4-padded
+            // uint4-padded, and by at least one byte: the kernel's batched
+            // lookup (direct_count<2>) reads lang2[base2 + rank] for windows
+            // that are no key too, up to index lang2.size() itself
+            constexpr auto lang2_words = [](size_t n) { return (uint32_t)((n + 16) / 16) * 4u; };
+            static_assert(lang2_words(0) * 4u > 0 && lang2_words(15) * 4u > 15 && lang2_words(16) * 4u > 16,
+                          "the language list must keep a padding byte past its end");
+            const uint32_t dwords = 64u + 1024u + lang2_words(lang2.size());
             const uint32_t hw4 = m->mode == 3 ? 0u : 64u * (uint32_t)S * (uint32_t)m->n_cls;
             if (score_lds_bytes(S, m->mode == 3 ? 3 : 4, image_words + dwords, false, hw4) * 2 <= 163840) {
                 m->direct_off = image_words;

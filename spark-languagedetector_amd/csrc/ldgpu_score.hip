@@ -976,18 +976,36 @@ __device__ __forceinline__ void direct_count(const ScoreParams& p, const WaveLds
         uint32_t w[kSub];
 #pragma unroll
         for (int k = 0; k < NK; ++k) w[k] = img[kBmp1Words + bmp2_word(x.lo[k])];
+        // any: the lane has a hit in one of its NK positions.  The rest of
+        // the function runs for those lanes only, so a wave without a 2-byte
+        // hit leaves in one branch instead of walking NK empty count branches.
+        bool any = false;
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
             // bit (lo & 31) of the word; the offset / width operands of v_bfe
             // take their low 5 bits, so no masking
             hit[k] = __builtin_amdgcn_ubfe(w[k], x.lo[k], 1) != 0u;
-            // the key's language by its rank among the 2-byte keys: read for
-            // hits only (a missing window costs one LDS read, not three)
-            lang[k] = 0;
-            if (hit[k])
-                lang[k] = l2[b2[bmp2_word(x.lo[k])] +
-                             __builtin_popcount(__builtin_amdgcn_ubfe(w[k], 0, x.lo[k]))];
+            any |= hit[k];
         }
+        if (!any) return;
+        // The key's language by its rank among the 2-byte keys, resolved for
+        // the lane's NK positions in one batch: every sub-block's rank base
+        // is read, then every language -- two LDS round trips per document,
+        // not two per hit sub-block.  A position that is no hit reads in range
+        // too (base + rank <= the number of 2-byte keys, and the host builder
+        // pads the language list by at least one byte past its end:
+        // ldgpu_api.hip, the direct tables); its language is not used.
+        uint32_t base[kSub];
+#pragma unroll
+        for (int k = 0; k < NK; ++k) base[k] = b2[bmp2_word(x.lo[k])];
+#pragma unroll
+        for (int k = 0; k < NK; ++k)
+            lang[k] = l2[base[k] + __builtin_popcount(__builtin_amdgcn_ubfe(w[k], 0, x.lo[k]))];
+        // the languages are complete here: the compiler otherwise sinks a
+        // sub-block's two reads into the branch that counts its hit, where
+        // they wait one after the other again
+#pragma unroll
+        for (int k = 0; k < NK; ++k) asm volatile("" : "+v"(lang[k]));
     }
     if constexpr (PACK) {
 #pragma unroll

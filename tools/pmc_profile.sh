@@ -2,6 +2,9 @@
 # rocprofv3 PMC passes (one counter group per run, never combined with tracing)
 # over a short bench run; summaries by tools/pmc_summary.py.
 # Usage: tools/pmc_profile.sh <outdir> [bench args...]
+# FILTER=<regex>: only the kernels it matches run under the counters
+# (rocprofv3 --kernel-include-regex; e.g. FILTER=score_kernel keeps torch's
+# generator kernels out of the passes)
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=$1; shift
@@ -20,7 +23,7 @@ for pass in "${PASSES[@]}"; do
   i=$((i+1))
   if [ -n "${ONLY:-}" ] && [[ " $ONLY " != *" $i "* ]]; then continue; fi
   echo "== pass $i: $pass"
-  timeout -s KILL 240 rocprofv3 --pmc $pass --output-format csv -d "$PWD/$OUT/pass$i" -o run -- python3 bench.py "$@" > "$OUT/pass$i.log" 2>&1
+  timeout -s KILL 240 rocprofv3 --pmc $pass ${FILTER:+--kernel-include-regex "$FILTER"} --output-format csv -d "$PWD/$OUT/pass$i" -o run -- python3 bench.py "$@" > "$OUT/pass$i.log" 2>&1
   rc=$?
   echo "rc=$rc"
   if [ $rc -ne 0 ]; then tail -5 "$OUT/pass$i.log"; exit $rc; fi
