@@ -1682,6 +1682,8 @@ void gram_lists(const ldgpu_model* m, ScoreParams& p, int mode) {
 
 // persistent grid: one wave per kScoreWaves documents, at most what is resident
 int score_grid(const ldgpu_model* m, int64_t n_docs) {
+    // (tests: a grid of a few workgroups puts many documents on each wave)
+    if (const char* g = diag_env("LDGPU_SCORE_GRID")) return std::max(1, atoi(g));
     const int64_t want = (n_docs + kScoreWaves - 1) / kScoreWaves;
     return (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)m->ctx->cus * m->wg_per_cu));
 }

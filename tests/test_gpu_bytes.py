@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import bytecorpus as B
+import geometry
 import ldoracle as O
 import ldoracle_c as OC
 from languagedetection import LanguageDetector, encoding
@@ -340,6 +341,8 @@ def test_packs_of_zero_and_ff_documents(L, n_keys):
     labels, _ = m.score(data, off, want_scores=False)
     assert np.array_equal(labels, ol), np.nonzero(labels != ol)[0][:10]
     assert len(np.unique(ol)) > 2
+    # 3000 documents are one per wave: packs form only on the tiled corpus
+    geometry.check_tiled_labels(m, data, off, ol, max(grams))
 
 
 # ---------------------------------------------------------------- direct tables

@@ -10,6 +10,7 @@ import math
 import numpy as np
 import pytest
 
+import geometry
 import ldoracle_c as OC
 from languagedetection import encoding
 from languagedetection.runtime import DeviceModel
@@ -215,9 +216,13 @@ def test_without_direct_tables(single, count_table, single_oracle, monkeypatch):
         assert np.array_equal(bits(scores), bits(os_))
 
 
-def test_packs(count_table):
+def test_packs(count_table, monkeypatch):
     """The same cases as packs of short documents (3..128 bytes, labels only):
-    one sub-block at a time, a hit counted into its own document's block."""
+    one sub-block at a time, a hit counted into its own document's block.
+    445 documents alone give every wave one document and no pack: the corpus
+    is scored again on one workgroup (diagnostics library, LDGPU_SCORE_GRID)
+    and, tiled, on the product grid, where the host model (tests/geometry.py)
+    says which documents share a pack."""
     docs, kinds = [], []
     for j in (0, 1, 31, 61):
         # a pack of four 64-byte documents: lane j a hit in every sub-block
@@ -243,6 +248,26 @@ def test_packs(count_table):
     labels, _ = m.score(data, off, want_scores=False)
     assert np.array_equal(labels, ol), np.nonzero(labels != ol)[0][:10]
     assert len(np.unique(ol)) > 2
+    # one workgroup: the sixteen quad documents are the first group of wave 0, each lane's four in one pack
+    pf = geometry.survey(off, max(GRAMS), geometry.SCORE_WAVES).pack_first
+    assert [pf[i:i + 4].tolist() for i in range(0, 16, 4)] == [[i] * 4 for i in range(0, 16, 4)]
+    monkeypatch.setenv("LDGPU_SCORE_GRID", "1")
+    diag = DeviceModel(count_table, L, GRAMS, variant="diag")
+    assert "packs" in diag.info()["layout"], diag.info()
+    labels, _ = diag.score(data, off, want_scores=False)
+    assert np.array_equal(labels, ol), np.nonzero(labels != ol)[0][:10]
+    # the product grid on the tiled corpus: in some period every quad, and
+    # every tail case with the document after it, is in one pack, at one,
+    # two or three workgroups per CU
+    to, times, cus = geometry.check_tiled_labels(m, data, off, ol, max(GRAMS))
+    tails = [16 + k2.index("tail%d" % n) for n in PACK_TAILS]
+    for w in (1, 2, 3):
+        pf = geometry.survey(to, max(GRAMS), geometry.product_waves(len(to) - 1, cus, w)).pack_first
+        pf = pf.reshape(times, len(docs))
+        for i in range(0, 16, 4):
+            assert ((pf[:, i:i + 4] == pf[:, i:i + 1]).all(axis=1) & (pf[:, i] >= 0)).any(), (w, i)
+        for i in tails:
+            assert ((pf[:, i] == pf[:, i + 1]) & (pf[:, i] >= 0)).any(), (w, i)
 
 
 def test_class_mode(single, monkeypatch):

@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import geometry
 import ldoracle as O
 import ldoracle_c as OC
 from conftest import GOLDEN
@@ -241,6 +242,8 @@ def test_packed_short_documents(L, grams, single):
     ol, _ = oracle_c(table, L, grams, data, off, scores=False)
     assert np.array_equal(labels, ol), np.nonzero(labels != ol)[0][:10]
     assert m.info()["mode"] == 2
+    # 3000 documents are one per wave: packs form only on the tiled corpus
+    geometry.check_tiled_labels(m, data, off, ol, max(grams))
 
 
 def test_packed_path_taken(monkeypatch, capfd):
@@ -858,6 +861,8 @@ def test_keyed_bloom_chunk_layout(chunks, buckets, grams, doc_range, monkeypatch
     labels, _ = m.score(data, off, want_scores=False)
     ol, _ = oracle_c(table, L, grams, data, off, scores=False)
     assert np.array_equal(labels, ol)
+    if doc_range == (20, 90):   # 2500 documents are one per wave: several only on the tiled corpus
+        geometry.check_tiled_labels(m, data, off, ol, max(grams))
 
 
 @pytest.mark.parametrize("form,grams,doc_range", [
@@ -896,6 +901,8 @@ def test_keyed_bloom_line_layout(form, grams, doc_range, monkeypatch):
     labels, _ = m.score(data, off, want_scores=False)
     ol, _ = oracle_c(table, L, grams, data, off, scores=False)
     assert np.array_equal(labels, ol)
+    if doc_range == (20, 90):   # 2500 documents are one per wave: several only on the tiled corpus
+        geometry.check_tiled_labels(m, data, off, ol, max(grams))
     monkeypatch.delenv("LDGPU_KB_LINES")
     plain, _ = DeviceModel(table, L, grams).score(data, off, want_scores=False)
     assert np.array_equal(plain, ol)
