@@ -162,6 +162,35 @@ int ldgpu_score_device(ldgpu_model* model, const uint8_t* d_bytes, int64_t n_byt
                        const int64_t* d_offsets, int64_t n_docs, int32_t* d_labels,
                        double* d_scores, void* stream);
 
+/* Top-k form of SCORE: per document the k best languages in order
+ * (out_top_labels [n_docs][k]) and, out_top_scores given ([n_docs][k],
+ * nullable), their fp64 scores bit for bit (a -0.0 stays -0.0, a NaN a NaN).
+ * The selection runs on the device: only [n_docs][k] leaves it.
+ * 1 <= k <= min(n_langs, LDGPU_MAX_TOPK), anything else is LDGPU_EINVAL.
+ * Order of a document's scores s[0 .. n_langs): language i comes before j if
+ * s[i] > s[j], or if they compare equal and i < j, where
+ *   -0.0 equals +0.0;
+ *   a NaN at index 0 comes first;
+ *   a NaN at any other index comes after every non-NaN value (-inf included),
+ *   NaNs among themselves by ascending index.
+ * Entry 0 is therefore the label ldgpu_score gives (breeze's first maximum,
+ * LanguageDetectorModel.scala:154); a document without a hit yields the labels
+ * 0, 1, .., k-1 with scores 0.0.  The reference has no such output.
+ * Argument checks, LDGPU_EROWLEN and the document-length limit, thread safety
+ * and the pipeline over pinned / pageable buffers are those of ldgpu_score. */
+#define LDGPU_MAX_TOPK 16
+int ldgpu_score_topk(ldgpu_model* model, const uint8_t* bytes, const int64_t* offsets,
+                     int64_t n_docs, int32_t k, int32_t* out_top_labels, double* out_top_scores);
+
+/* Device-resident variant, asynchronous on `stream` under the rules of
+ * ldgpu_score_device.  d_top_labels [n_docs][k], d_top_scores nullable
+ * [n_docs][k].  The documents are scored in chunks into stream-ordered
+ * scratch (at most 256 MiB of scores, chunk x n_langs doubles) and each chunk's
+ * rows selected from there: the full score matrix never exists. */
+int ldgpu_score_topk_device(ldgpu_model* model, const uint8_t* d_bytes, int64_t n_bytes,
+                            const int64_t* d_offsets, int64_t n_docs, int32_t k,
+                            int32_t* d_top_labels, double* d_top_scores, void* stream);
+
 /* -------------------------------------------------------------------- FIT */
 typedef struct ldgpu_counts ldgpu_counts;
 

@@ -240,6 +240,9 @@ struct ScoreStage {
     hipEvent_t done = nullptr;
     DevBuf bytes, offsets, labels, scores;
     HostBuf h_bytes, h_offsets, h_labels, h_scores;
+    // top-k calls (ldgpu_score_topk): the chunk's [nd][k] labels and scores
+    DevBuf top_labels, top_scores;
+    HostBuf h_top_labels, h_top_scores;
     int64_t d0 = 0, nd = 0;
     bool busy = false;
 };
@@ -340,8 +343,9 @@ namespace {
 void pipe_destroy(ScorePipe* pp) {
     for (auto& st : pp->stage) {
         if (st.stream) (void)hipStreamSynchronize(st.stream);
-        for (DevBuf* b : {&st.bytes, &st.offsets, &st.labels, &st.scores}) b->release();
-        for (HostBuf* b : {&st.h_bytes, &st.h_offsets, &st.h_labels, &st.h_scores}) b->release();
+        for (DevBuf* b : {&st.bytes, &st.offsets, &st.labels, &st.scores, &st.top_labels, &st.top_scores}) b->release();
+        for (HostBuf* b : {&st.h_bytes, &st.h_offsets, &st.h_labels, &st.h_scores, &st.h_top_labels, &st.h_top_scores})
+            b->release();
         if (st.done) (void)hipEventDestroy(st.done);
         if (st.stream) (void)hipStreamDestroy(st.stream);
     }
@@ -1913,8 +1917,76 @@ extern "C" int ldgpu_score_device(ldgpu_model* m, const uint8_t* d_bytes, int64_
 }
 
 namespace {
+// Top-k calls score a chunk of documents into scratch of this many bytes of
+// scores at most (chunk x L doubles) and select from there.  (The best of 16 /
+// 64 / 256 MiB on configs 2 and 5, tools/bench_topk.py: DESIGN.md Measurement.)
+constexpr int64_t kTopkScratchBytes = 256ll << 20;
+int64_t topk_chunk_docs(int32_t L) {
+    // (tests: chunks of a few documents)
+    if (const char* c = diag_env("LDGPU_TOPK_CHUNK_DOCS")) return std::max<int64_t>(1, atoll(c));
+    return std::max<int64_t>(1, kTopkScratchBytes / ((int64_t)sizeof(double) * L));
+}
+int check_topk(const ldgpu_model* m, int32_t k) {
+    if (k < 1 || k > m->L || k > LDGPU_MAX_TOPK)
+        return fail(LDGPU_EINVAL, "k = %d outside [1, min(n_langs = %d, %d)]", k, m->L, LDGPU_MAX_TOPK);
+    return LDGPU_OK;
+}
+}  // namespace
+
+// Chunks of documents (sub-ranges of d_offsets, whose entries are absolute into
+// d_bytes: nothing is read back) scored into stream-ordered scratch through
+// score_launch -- every model kind's own scores path -- then selected.
+extern "C" int ldgpu_score_topk_device(ldgpu_model* m, const uint8_t* d_bytes, int64_t n_bytes,
+                                       const int64_t* d_offsets, int64_t n_docs, int32_t k, int32_t* d_top_labels,
+                                       double* d_top_scores, void* stream) {
+    if (!m) return fail(LDGPU_EINVAL, "model is NULL");
+    if (n_docs < 0) return fail(LDGPU_EINVAL, "n_docs < 0");
+    if (int rc = check_topk(m, k)) return rc;
+    if (n_docs > 0 && (!d_offsets || !d_top_labels || (n_bytes > 0 && !d_bytes)))
+        return fail(LDGPU_EINVAL, "device pointer is NULL");
+    if (((uintptr_t)d_bytes & 3) != 0) return fail(LDGPU_EINVAL, "d_bytes must be 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    const int64_t chunk = topk_chunk_docs(m->L);
+    for (int64_t d0 = 0; d0 < n_docs; d0 += chunk) {
+        const int64_t nd = std::min(chunk, n_docs - d0);
+        const size_t score_bytes = sizeof(double) * (size_t)nd * m->L;
+        char* scratch = nullptr;
+        HIP_TRY(hipMallocAsync((void**)&scratch, score_bytes + sizeof(int32_t) * (size_t)nd, st));
+        double* sc = (double*)scratch;
+        int rc = score_launch(m, d_bytes, n_bytes, d_offsets + d0, nd, (int32_t*)(scratch + score_bytes), sc, m->d_err,
+                              st);
+        hipError_t e = hipSuccess;
+        if (!rc) {
+            TopkParams t{};
+            t.scores = sc;
+            t.stride = m->L;
+            t.n = nd;
+            t.L = m->L;
+            t.k = k;
+            t.top_labels = d_top_labels + d0 * k;
+            t.top_scores = d_top_scores ? d_top_scores + d0 * k : nullptr;
+            e = launch_topk(t, m->ctx->cus, st);
+        }
+        (void)hipFreeAsync(scratch, st);
+        if (rc) return rc;
+        HIP_TRY(e);
+    }
+    if (m->has_bad && n_docs > 0) {
+        if (int rc = check_row_error(m, m->d_err, st)) return rc;
+    }
+    return ok();
+}
+
+namespace {
+// the top-k form's outputs ([n_docs][k]; scores nullable)
+struct TopkOut {
+    int32_t k;
+    int32_t* labels;
+    double* scores;
+};
 int score_host(ldgpu_model* m, ScorePipe* pp, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs,
-               int32_t* out_labels, double* out_scores);
+               int32_t* out_labels, double* out_scores, const TopkOut* tk = nullptr);
 }  // namespace
 
 // Thread-safe and concurrent: each call scores on a pipeline (two streams,
@@ -1940,21 +2012,56 @@ extern "C" int ldgpu_score(ldgpu_model* m, const uint8_t* bytes, const int64_t* 
     return ok();
 }
 
+extern "C" int ldgpu_score_topk(ldgpu_model* m, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs,
+                                int32_t k, int32_t* out_top_labels, double* out_top_scores) {
+    if (!m) return fail(LDGPU_EINVAL, "model is NULL");
+    if (int rc = check_offsets(offsets, n_docs)) return rc;
+    if (int rc = check_topk(m, k)) return rc;
+    if (n_docs == 0) return ok();
+    if (!out_top_labels) return fail(LDGPU_EINVAL, "out_top_labels is NULL");
+    if (!bytes && offsets[n_docs] > offsets[0]) return fail(LDGPU_EINVAL, "bytes is NULL");
+    for (int64_t d = 0; d < n_docs; ++d)
+        if (offsets[d + 1] - offsets[d] >= kMaxDocBytes)
+            return fail(LDGPU_EUNSUPPORTED, "document %lld has %lld bytes: the device path's limit is %lld",
+                        (long long)d, (long long)(offsets[d + 1] - offsets[d]), (long long)kMaxDocBytes - 1);
+    ldgpu_ctx* c = m->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    ScorePipe* pp = pipe_acquire(c);
+    if (!pp) return LDGPU_EDEVICE;
+    const TopkOut tk{k, out_top_labels, out_top_scores};
+    const int rc = score_host(m, pp, bytes, offsets, n_docs, nullptr, nullptr, &tk);
+    pipe_release(c, pp);
+    if (rc) return rc;
+    return ok();
+}
+
 namespace {
 int score_host(ldgpu_model* m, ScorePipe* pp, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs,
-               int32_t* out_labels, double* out_scores) {
+               int32_t* out_labels, double* out_scores, const TopkOut* tk) {
     // Two-stage pipeline over chunks of documents, one stream per stage: while
     // the GPU copies and scores chunk i, the host stages chunk i + 1 into the
     // other stage's pinned buffers (a caller buffer already in pinned memory is
     // copied from directly) and hands back the labels of chunk i - 1.
-    const int64_t kChunkBytes = 64ll << 20, kChunkDocs = 1ll << 20;
+    // Top-k form (tk): every chunk is scored into the stage's score buffer
+    // (at most kTopkScratchBytes of it), its rows selected on the device
+    // (launch_topk), and only the chunk's [nd][k] labels and scores copied
+    // back; the stage's [nd] labels serve score_launch alone.
+    const int64_t kChunkBytes = 64ll << 20;
+    const int64_t kChunkDocs = tk ? std::min<int64_t>(1ll << 20, topk_chunk_docs(m->L)) : 1ll << 20;
     const bool pinned_in = nb_total_pinned(bytes, offsets, n_docs);
-    const bool pinned_out = is_pinned(out_labels) && (!out_scores || is_pinned(out_scores));
+    const bool pinned_out = tk ? is_pinned(tk->labels) && (!tk->scores || is_pinned(tk->scores))
+                               : is_pinned(out_labels) && (!out_scores || is_pinned(out_scores));
+    const bool want_scores = out_scores || tk;
     auto retire = [&](ScoreStage& st) -> int {
         if (!st.busy) return LDGPU_OK;
         HIP_TRY(hipEventSynchronize(st.done));
         st.busy = false;
-        if (!pinned_out) {
+        if (tk) {
+            if (!pinned_out) {
+                memcpy(tk->labels + st.d0 * tk->k, st.h_top_labels.p, sizeof(int32_t) * st.nd * tk->k);
+                if (tk->scores) memcpy(tk->scores + st.d0 * tk->k, st.h_top_scores.p, sizeof(double) * st.nd * tk->k);
+            }
+        } else if (!pinned_out) {
             memcpy(out_labels + st.d0, st.h_labels.p, sizeof(int32_t) * st.nd);
             if (out_scores) par_memcpy(out_scores + st.d0 * m->L, st.h_scores.p, sizeof(double) * st.nd * m->L);
         }
@@ -1967,7 +2074,7 @@ int score_host(ldgpu_model* m, ScorePipe* pp, const uint8_t* bytes, const int64_
         HIP_TRY(st.bytes.ensure((size_t)nb + 16));
         HIP_TRY(st.offsets.ensure(sizeof(int64_t) * (nd + 1)));
         HIP_TRY(st.labels.ensure(sizeof(int32_t) * nd));
-        if (out_scores) HIP_TRY(st.scores.ensure(sizeof(double) * nd * m->L));
+        if (want_scores) HIP_TRY(st.scores.ensure(sizeof(double) * nd * m->L));
         HIP_TRY(st.h_offsets.ensure(sizeof(int64_t) * (nd + 1)));
         int64_t* ho = (int64_t*)st.h_offsets.p;
         for (int64_t i = 0; i <= nd; ++i) ho[i] = offsets[d0 + i] - b0;
@@ -1982,9 +2089,40 @@ int score_host(ldgpu_model* m, ScorePipe* pp, const uint8_t* bytes, const int64_
         // (class mode included: its replay of ambiguous documents reads no
         // count back, so the staging of the next chunk still overlaps)
         if (int r = score_launch(m, (const uint8_t*)st.bytes.p, nb, (const int64_t*)st.offsets.p, nd,
-                                 (int32_t*)st.labels.p, out_scores ? (double*)st.scores.p : nullptr, pp->d_err,
+                                 (int32_t*)st.labels.p, want_scores ? (double*)st.scores.p : nullptr, pp->d_err,
                                  st.stream))
             return r;
+        if (tk) {
+            const size_t nl = sizeof(int32_t) * nd * tk->k, ns = sizeof(double) * nd * tk->k;
+            HIP_TRY(st.top_labels.ensure(nl));
+            if (tk->scores) HIP_TRY(st.top_scores.ensure(ns));
+            TopkParams t{};
+            t.scores = (const double*)st.scores.p;
+            t.stride = m->L;
+            t.n = nd;
+            t.L = m->L;
+            t.k = tk->k;
+            t.top_labels = (int32_t*)st.top_labels.p;
+            t.top_scores = tk->scores ? (double*)st.top_scores.p : nullptr;
+            HIP_TRY(launch_topk(t, m->ctx->cus, st.stream));
+            int32_t* tl_dst = tk->labels + d0 * tk->k;
+            double* ts_dst = tk->scores ? tk->scores + d0 * tk->k : nullptr;
+            if (!pinned_out) {
+                HIP_TRY(st.h_top_labels.ensure(nl));
+                tl_dst = (int32_t*)st.h_top_labels.p;
+                if (tk->scores) {
+                    HIP_TRY(st.h_top_scores.ensure(ns));
+                    ts_dst = (double*)st.h_top_scores.p;
+                }
+            }
+            HIP_TRY(hipMemcpyAsync(tl_dst, st.top_labels.p, nl, hipMemcpyDeviceToHost, st.stream));
+            if (tk->scores) HIP_TRY(hipMemcpyAsync(ts_dst, st.top_scores.p, ns, hipMemcpyDeviceToHost, st.stream));
+            HIP_TRY(hipEventRecord(st.done, st.stream));
+            st.d0 = d0;
+            st.nd = nd;
+            st.busy = true;
+            return LDGPU_OK;
+        }
         int32_t* lab_dst = out_labels + d0;
         double* sc_dst = out_scores ? out_scores + d0 * m->L : nullptr;
         if (!pinned_out) {

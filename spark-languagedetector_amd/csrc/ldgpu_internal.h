@@ -224,6 +224,22 @@ hipError_t launch_long_flag(const LongFlagParams& p, int cus, hipStream_t stream
 // labels / maxima at lab + b n, best + b n)
 hipError_t launch_combine_blocks(int64_t n, int nb, const int32_t* lab, const double* best, int32_t* out,
                                  hipStream_t stream);
+// Top-k of every row of a score matrix (ldgpu_topk.hip): the k best languages
+// in order (the order rule of ldgpu_score_topk, include/ldgpu.h) and,
+// top_scores given, their scores bit for bit.  1 <= k <= min(L, kMaxTopk),
+// L <= kTopkMaxLangs, stride >= L.
+struct TopkParams {
+    const double* scores;       // [n] rows of L scores, `stride` doubles apart
+    int64_t stride;
+    int64_t n;
+    int32_t L;
+    int32_t k;
+    int32_t* top_labels;        // [n][k]
+    double* top_scores;         // nullable [n][k]
+};
+constexpr int kMaxTopk = 16;          // LDGPU_MAX_TOPK
+constexpr int kTopkMaxLangs = 4096;   // LDGPU_MAX_LANGS
+hipError_t launch_topk(const TopkParams& p, int cus, hipStream_t stream);
 // sets the dynamic-LDS limit and returns the resident workgroups per CU
 // (chunks: a count-mode table's keyed bloom in the chunk layout)
 hipError_t score_prepare(int slices, int mode, bool lds_bloom, bool chunks, size_t lds_bytes, int* blocks_per_cu);

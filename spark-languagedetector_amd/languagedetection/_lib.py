@@ -32,6 +32,7 @@ LDGPU_ENODEV = 6
 MAX_GRAM = 2147483647  # SCORE tables: any gram length (beyond 15: the general-key table)
 MAX_FIT_GRAM = 16777215  # FIT counting (grams of 8..15 bytes: two words; longer: the general-key table)
 MAX_LANGS = 4096
+MAX_TOPK = 16  # LDGPU_MAX_TOPK
 # ldgpu_model_layout flags
 LAYOUT_FLAGS = {"lds_bloom": 0x01, "keyed_bloom": 0x02, "keyed_bloom_lines": 0x04, "buckets": 0x08,
                 "wide_keys": 0x10, "direct": 0x20, "packs": 0x40, "lang_blocks": 0x80,
@@ -64,6 +65,8 @@ SIGNATURES = [
     ("ldgpu_model_langs", ctypes.c_int, [_p, _pi32]),
     ("ldgpu_score", ctypes.c_int, [_p, _p, _p, _i64, _p, _p]),
     ("ldgpu_score_device", ctypes.c_int, [_p, _p, _i64, _p, _i64, _p, _p, _p]),
+    ("ldgpu_score_topk", ctypes.c_int, [_p, _p, _p, _i64, _i32, _p, _p]),
+    ("ldgpu_score_topk_device", ctypes.c_int, [_p, _p, _i64, _p, _i64, _i32, _p, _p, _p]),
     ("ldgpu_counts_create", ctypes.c_int, [_p, _i32, _p, _i32, _i64, _pp]),
     ("ldgpu_counts_destroy", ctypes.c_int, [_p]),
     ("ldgpu_counts_langs", ctypes.c_int, [_p, _pi32]),
@@ -198,8 +201,8 @@ def device_count() -> int:
 
 # the sources the library is built from, in the Makefile's PROV order
 _PROV = ["csrc/ldgpu_api.hip", "csrc/ldgpu_score.hip", "csrc/ldgpu_fit.hip", "csrc/ldgpu_general.hip",
-         "csrc/ldgpu_long.hip", "csrc/ldgpu_replay.hip", "csrc/ldgpu_pre.hip", "csrc/ldgpu_common.h",
-         "csrc/ldgpu_internal.h", "csrc/ldgpu_fit.h", "../include/ldgpu.h"]
+         "csrc/ldgpu_long.hip", "csrc/ldgpu_replay.hip", "csrc/ldgpu_pre.hip", "csrc/ldgpu_topk.hip",
+         "csrc/ldgpu_common.h", "csrc/ldgpu_internal.h", "csrc/ldgpu_fit.h", "../include/ldgpu.h"]
 
 
 def tree_source_hash() -> str:

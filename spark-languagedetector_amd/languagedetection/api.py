@@ -136,6 +136,39 @@ class LanguageDetectorModel(_Params):
         out[self.getOutputCol()] = [self.supportedLanguages[i] for i in labels]
         return out
 
+    # Top-k output (an addition: the reference returns the label alone).  Entry
+    # 0 is transform's language; the order is languagedetection.topk's.
+    def predict_topk(self, texts: Sequence[str], k: int) -> Tuple[List[List[str]], np.ndarray]:
+        """(the k best languages of every text in order, their scores fp64[n, k])."""
+        for t in texts:
+            if t is None:
+                raise NullPointerException("text is null")
+        data, offsets = encoding.pack_score(texts)
+        labels, scores = self.device_model().score_topk(data, offsets, k, want_scores=True)
+        return [[self.supportedLanguages[i] for i in row] for row in labels], scores
+
+    def transformTopK(self, dataset, k: int, candidatesCol: str = "lang_candidates",
+                      scoresCol: str = "lang_scores"):
+        """Append candidatesCol (the k best languages, in order) and scoresCol
+        (their scores) for every row; an existing column of either name is
+        rejected as transformSchema rejects outputCol."""
+        import pandas as pd
+        df = dataset if isinstance(dataset, pd.DataFrame) else pd.DataFrame(dataset)
+        schema = self._schema_of(df)
+        in_type = schema.get(self.getInputCol())
+        if in_type is None:
+            raise ValueError(f"Field \"{self.getInputCol()}\" does not exist.")
+        if in_type != "string":
+            raise ValueError(f"requirement failed: Input type must be StringType but got {in_type}.")
+        for c in (candidatesCol, scoresCol):
+            if c in schema:
+                raise ValueError(f"requirement failed: Column {c} already exists.")
+        langs, scores = self.predict_topk(list(df[self.getInputCol()]), k)
+        out = df.copy()
+        out[candidatesCol] = pd.Series(langs, index=out.index, dtype=object)
+        out[scoresCol] = pd.Series([row.tolist() for row in scores], index=out.index, dtype=object)
+        return out
+
     # persistence (LanguageDetectorModel.scala:24-105): the reference's layout
     def write(self) -> "LanguageDetectorModelWriter":
         return LanguageDetectorModelWriter(self)

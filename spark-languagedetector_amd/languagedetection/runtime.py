@@ -148,6 +148,36 @@ class DeviceModel(_Owner):
                                                ctypes.c_void_p(d_scores) if d_scores else None,
                                                ctypes.c_void_p(st) if st else None))
 
+    def score_topk(self, data: np.ndarray, offsets: np.ndarray, k: int, want_scores: bool = True,
+                   out_labels: Optional[np.ndarray] = None, out_scores: Optional[np.ndarray] = None
+                   ) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+        """Host buffers -> (the k best languages in order int32[n, k], their
+        scores fp64[n, k] or None), selected on the device (ldgpu_score_topk;
+        the order: languagedetection.topk).  `out_labels` / `out_scores` (e.g.
+        PinnedArray arrays) receive the results."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n, k = max(len(offsets) - 1, 0), int(k)
+        shape = (n, max(k, 0))
+        labels = np.zeros(shape, dtype=np.int32) if out_labels is None else out_labels
+        scores = (np.zeros(shape, dtype=np.float64) if out_scores is None else out_scores) if want_scores else None
+        assert labels.dtype == np.int32 and labels.shape == shape and labels.flags.c_contiguous
+        assert scores is None or (scores.dtype == np.float64 and scores.shape == shape and scores.flags.c_contiguous)
+        self._check(self.lib.ldgpu_score_topk(self.h, _ptr(data), _ptr(offsets), len(offsets) - 1, k, _ptr(labels),
+                                              _ptr(scores)))
+        return labels, scores
+
+    def score_topk_device(self, d_bytes: int, n_bytes: int, d_offsets: int, n_docs: int, k: int, d_top_labels: int,
+                          d_top_scores: int = 0, stream: Optional[int] = None) -> None:
+        """Device pointers -> the [n_docs, k] labels (and scores) in place,
+        async on `stream` as score_device (ldgpu_score_topk_device)."""
+        st = self.stream() if stream is None else stream
+        self._check(self.lib.ldgpu_score_topk_device(self.h, ctypes.c_void_p(d_bytes), n_bytes,
+                                                     ctypes.c_void_p(d_offsets), n_docs, int(k),
+                                                     ctypes.c_void_p(d_top_labels),
+                                                     ctypes.c_void_p(d_top_scores) if d_top_scores else None,
+                                                     ctypes.c_void_p(st) if st else None))
+
 
 class DeviceCounts(_Owner):
     """A (gram, language) -> count table on one GPU (computeGrams + reduceGrams)."""
