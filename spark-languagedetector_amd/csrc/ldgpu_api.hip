@@ -659,9 +659,10 @@ void model_free(ldgpu_model* m) {
     model_free(m->short_m);
     if (m->ctx) (void)hipSetDevice(m->ctx->device);
     if (m->d_stats) {
-        unsigned long long st[2] = {0, 0};
+        unsigned long long st[4] = {0, 0, 0, 0};
         if (hipMemcpy(st, m->d_stats, sizeof st, hipMemcpyDeviceToHost) == hipSuccess)
-            fprintf(stderr, "[ldgpu] stats: candidates verified %llu, hits %llu\n", st[0], st[1]);
+            fprintf(stderr, "[ldgpu] stats: candidates verified %llu, hits %llu, documents scanned %llu, "
+                            "store-loop iterations %llu\n", st[0], st[1], st[2], st[3]);
         (void)hipFree(m->d_stats);
     }
     for (void* p : {(void*)m->d_slots, (void*)m->d_wslots, (void*)m->d_buckets, (void*)m->d_filter, (void*)m->d_masks, (void*)m->d_vals, (void*)m->d_rows,
@@ -1598,8 +1599,8 @@ int model_build(ldgpu_ctx* ctx, int32_t n_langs, const int32_t* gram_lengths, in
     if (const char* ov = diag_env("LDGPU_WG_PER_CU")) m->wg_per_cu = std::max(1, atoi(ov));
     if (const char* ab = diag_env("LDGPU_ABLATE")) m->ablate = atoi(ab);
     if (diag_env("LDGPU_STATS") && e == hipSuccess) {
-        e = hipMalloc((void**)&m->d_stats, 2 * sizeof(unsigned long long));
-        if (e == hipSuccess) e = hipMemset(m->d_stats, 0, 2 * sizeof(unsigned long long));
+        e = hipMalloc((void**)&m->d_stats, 4 * sizeof(unsigned long long));
+        if (e == hipSuccess) e = hipMemset(m->d_stats, 0, 4 * sizeof(unsigned long long));
     }
     if (diag_env("LDGPU_DEBUG"))
         fprintf(stderr, "[ldgpu] model: keys=%lld mode=%d direct=%u slices=%d bloom_words=%llu lds_bloom=%d lds=%zu B "

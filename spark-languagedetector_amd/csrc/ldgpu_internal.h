@@ -51,7 +51,8 @@ struct ScoreParams {
     int32_t n_cls;
     uint32_t hit_words;         // class mode: the hit area per wave (64 S n_cls words), sized by the table
     int32_t* err;               // bit 0: a window hit a wrong-length row; bit 1: doc too long
-    unsigned long long* stats;  // diagnostics build (-DLDGPU_STATS, env LDGPU_STATS): [0] candidates verified, [1] hits
+    unsigned long long* stats;  // diagnostics build (-DLDGPU_STATS, env LDGPU_STATS): [0] candidates verified, [1] hits,
+                                // [2] documents queued by scan_append, [3] its store-loop iterations
     int32_t L;
     int32_t ablate;             // diagnostics build only (LDGPU_ABLATE; compiled out otherwise): bit 0 skip
                                 // verify/accumulate, bit 1 skip probe, bit 2 skip the hit replay, bit 3

@@ -19,8 +19,10 @@
 //              instead.  Each gram length n then tests one bit of a word (a
 //              24-bit multiply and a bit extract), and a ballot appends the
 //              candidates to a per-wave LDS queue with mbcnt, so the queue is
-//              in reference order: n outer, position inner.
-//   verify     64 queued keys at a time probe the global table (2-choice
+//              in reference order: n outer, position inner.  Count and class
+//              mode need no order: on their split-verify path one wave scan
+//              queues a document's candidates of lengths 3..7 (scan_append).
+//   verify    64 queued keys at a time probe the global table (2-choice
 //              cuckoo slots, 5-slot buckets for big count-mode tables, a
 //              two-word table for keys of 8..15 bytes).
 //   accumulate count mode (every row one shared value): per-language hit
@@ -1125,6 +1127,110 @@ __device__ __forceinline__ void probe_count(const ScoreParams& p, const WaveLds&
     append_sb(wl.queue, qn, m, N, 0, lane);
 }
 
+// Count / class mode, split verify with the prefix Bloom in LDS: the queue's
+// (length, position) order buys nothing (counts are order-free), so the
+// candidates of lengths 3..7 are queued by ONE wave scan instead of a ballot,
+// a popcount and an exec-masked store per (length, sub-block).
+//   gather  bit 8 k + (N - 3) of the lane's cm = the window of length N at its
+//           position 64 k + lane passes the filter -- no ballot, no SGPR mask;
+//           then the per-lane tail cut: sub-block k keeps its lengths
+//           N <= len - 64 k - lane, the windows that lie inside the document
+//   scan    c = popcount(cm); inclusive wave sum of c by DPP (the shape of
+//           wave_max_u32); total = lane 63's
+//   store   lane's c entries from queue word sum - c, lowest bit first; the
+//           loop runs max(c) times with the finished lanes masked off
+// Returns false, with nothing queued, when the document has more than
+// kQueueCap candidates: the caller then takes the per-length path, which
+// flushes in the middle of the document.
+#ifndef LDGPU_SCAN_APPEND
+#define LDGPU_SCAN_APPEND 1
+#endif
+
+// (t << SH) | c in one VALU op (the compiler otherwise shifts every bit by
+// itself and merges them with v_or3: six ops per length where four do)
+template <int SH>
+__device__ __forceinline__ uint32_t lshl_or(uint32_t t, uint32_t c) {
+    uint32_t r;
+    asm("v_lshl_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(t), "n"(SH), "v"(c));
+    return r;
+}
+
+template <int N>
+__device__ __forceinline__ void scan_bits(const FWords& f, const Windows& x, uint32_t fm, uint32_t& cm) {
+    if (!((fm >> N) & 1u)) return;
+#pragma unroll
+    for (int k = 0; k < kSub; ++k) {
+        const uint32_t in = __builtin_amdgcn_alignbit(x.hi[k], x.lo[k], pf_shift(N));
+        const uint32_t t = __builtin_amdgcn_ubfe(f.w3[k], mulhi24(in, pf_mult(N)), 1);
+        cm = k == 0 ? lshl_or<N - 3>(t, cm)
+                    : (k == 1 ? lshl_or<8 + N - 3>(t, cm) : (k == 2 ? lshl_or<16 + N - 3>(t, cm) : lshl_or<24 + N - 3>(t, cm)));
+    }
+}
+
+__device__ __forceinline__ uint32_t wave_scan_u32(uint32_t v) {  // inclusive prefix sum
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);  // row_shr:1
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);  // row_shr:2
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);  // row_shr:4
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);  // row_shr:8
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);  // row_bcast:15
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);  // row_bcast:31
+    return v;
+}
+
+template <bool FULL>
+__device__ __forceinline__ bool scan_append(const ScoreParams& p, const WaveLds& wl, const FWords& f,
+                                            const Windows& x, int32_t len, int lane, int& qn, uint32_t fm) {
+    uint32_t cm = 0;
+    if (!ablated(p, 16)) {
+        scan_bits<3>(f, x, fm, cm);
+        scan_bits<4>(f, x, fm, cm);
+        scan_bits<5>(f, x, fm, cm);
+        scan_bits<6>(f, x, fm, cm);
+        scan_bits<7>(f, x, fm, cm);
+    }
+    // tail cut: byte k of cm keeps its low clamp(len - 64 k - lane - 2, 0, 5)
+    // bits (lengths 3 .. len - 64 k - lane).  FULL: more than 192 windows of
+    // every length, so only the last sub-block is cut -- cm's top byte
+    const int32_t left = len - 2 - lane;
+    if constexpr (FULL) {
+        cm = __builtin_amdgcn_ubfe(cm, 0, (uint32_t)min(max(left - 192 + 24, 24), 29));
+    } else {
+        uint32_t keep = 0;
+#pragma unroll
+        for (int k = 0; k < kSub; ++k) keep |= ((1u << min(max(left - 64 * k, 0), 5)) - 1u) << (8 * k);
+        cm &= keep;
+    }
+    const uint32_t c = (uint32_t)__builtin_popcount(cm);
+    const uint32_t sum = wave_scan_u32(c);
+    const uint32_t total = rdlane(sum, 63);
+    if (total > (uint32_t)kQueueCap) return false;
+#ifdef LDGPU_STATS
+    if (p.stats) {  // documents scanned, store-loop iterations (the largest c of a lane)
+        const uint32_t it = wave_max_u32(c);
+        if (lane == 0) {
+            atomicAdd(&p.stats[2], 1ull);
+            atomicAdd(&p.stats[3], (unsigned long long)it);
+        }
+    }
+#endif
+    if (total) {
+        // (opaque lane: see append_sb)
+        uint32_t l = (uint32_t)lane;
+        asm volatile("" : "+v"(l));
+        const uint32_t tag = l + (3u << kPosBits);
+        uint32_t at = (uint32_t)(uintptr_t)wl.queue + 4u * (sum - c);  // LDS offset of the lane's first entry
+        while (cm) {
+            // bit j = 8 k + (N - 3): the entry N << kPosBits | 64 k + lane
+            const uint32_t j = (uint32_t)__builtin_ctz(cm);
+            *(lds_u32*)(size_t)at = ((j & 7u) << kPosBits) + (((j >> 3) << 6) + tag);
+            at += 4u;
+            cm &= cm - 1u;
+        }
+    }
+    qn = (int)total;
+    return true;
+}
+
 template <bool FULL, int S, bool STAGED, int KEYED, bool WIDE, int MODE = 3>
 __device__ __forceinline__ void probe_count_all(const ScoreParams& p, const WaveLds& wl, const uint32_t* img,
                                                 const FWords& f, const Windows& x, int32_t len, int lane, int& qn,
@@ -1154,11 +1260,20 @@ __device__ __forceinline__ void probe_count_all(const ScoreParams& p, const Wave
         probe_count<1, FULL, S, STAGED, KEYED, WIDE, MODE>(p, wl, img, f, x, len, lane, qn, src, fm, kw);
         probe_count<2, FULL, S, STAGED, KEYED, WIDE, MODE>(p, wl, img, f, x, len, lane, qn, src, fm, kw);
     }
-    probe_count<3, FULL, S, STAGED, KEYED, WIDE, MODE>(p, wl, img, f, x, len, lane, qn, src, fm, kw);
-    probe_count<4, FULL, S, STAGED, KEYED, WIDE, MODE>(p, wl, img, f, x, len, lane, qn, src, fm, kw);
-    probe_count<5, FULL, S, STAGED, KEYED, WIDE, MODE>(p, wl, img, f, x, len, lane, qn, src, fm, kw);
-    probe_count<6, FULL, S, STAGED, KEYED, WIDE, MODE>(p, wl, img, f, x, len, lane, qn, src, fm, kw);
-    probe_count<7, FULL, S, STAGED, KEYED, WIDE, MODE>(p, wl, img, f, x, len, lane, qn, src, fm, kw);
+    // lengths 3..7: one wave scan (scan_append) on the split path of the LDS
+    // prefix Bloom; the per-length path otherwise, and for a document with
+    // more candidates than the queue holds
+    bool scanned = false;
+    if constexpr (LDGPU_SCAN_APPEND && KEYED == 0 && !WIDE && LDGPU_BLOOM_BITS == 1) {
+        if (split) scanned = scan_append<FULL>(p, wl, f, x, len, lane, qn, fm);
+    }
+    if (!scanned) {
+        probe_count<3, FULL, S, STAGED, KEYED, WIDE, MODE>(p, wl, img, f, x, len, lane, qn, src, fm, kw);
+        probe_count<4, FULL, S, STAGED, KEYED, WIDE, MODE>(p, wl, img, f, x, len, lane, qn, src, fm, kw);
+        probe_count<5, FULL, S, STAGED, KEYED, WIDE, MODE>(p, wl, img, f, x, len, lane, qn, src, fm, kw);
+        probe_count<6, FULL, S, STAGED, KEYED, WIDE, MODE>(p, wl, img, f, x, len, lane, qn, src, fm, kw);
+        probe_count<7, FULL, S, STAGED, KEYED, WIDE, MODE>(p, wl, img, f, x, len, lane, qn, src, fm, kw);
+    }
     // wide gram lengths 8..15: one loop, the length a scalar (their filter
     // bits use the first seven bytes: the same two tests as length 7)
     for (uint32_t wm = WIDE ? (fm >> 8) & 0xffu : 0u; wm; wm &= wm - 1u) {
