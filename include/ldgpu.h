@@ -191,6 +191,56 @@ int ldgpu_score_topk_device(ldgpu_model* model, const uint8_t* d_bytes, int64_t 
                             const int64_t* d_offsets, int64_t n_docs, int32_t k,
                             int32_t* d_top_labels, double* d_top_scores, void* stream);
 
+/* Span form of SCORE, for mixed-language documents: every document is cut on
+ * the device into overlapping spans of `width` bytes every `stride` bytes, and
+ * every span is scored as a document of its own.  The reference has no such
+ * output.  width >= 1 and 1 <= stride <= width, anything else is LDGPU_EINVAL;
+ * width >= 2^28 (the document limit of ldgpu_score) is LDGPU_EUNSUPPORTED.
+ *   Spans of a document of len bytes: one if len <= width, otherwise
+ *   1 + ceil((len - width) / stride).  Span j is bytes [j stride,
+ *   min(j stride + width, len)) of the document: every span of a document
+ *   longer than width holds at least one byte; an empty document has one
+ *   empty span.
+ *   The label and the score row of a span are exactly what ldgpu_score gives
+ *   for a document holding that slice: partial windows of a slice shorter
+ *   than a gram length, label 0 without a hit, the tie and NaN rules, scores
+ *   bit for bit.
+ *   Spans are numbered document by document: span_offsets[d] is the index of
+ *   document d's first span, span_offsets[0] = 0 and span_offsets[n_docs] the
+ *   number of spans (int64: at stride 1 of the order of the corpus bytes).
+ * ldgpu_span_offsets is host arithmetic (no context, no GPU; the offsets are
+ * checked as by ldgpu_score); ldgpu_span_offsets_device the same on device
+ * arrays, asynchronous on `stream`, offsets trusted. */
+int ldgpu_span_offsets(const int64_t* offsets, int64_t n_docs, int32_t width, int32_t stride,
+                       int64_t* span_offsets /* [n_docs + 1] */);
+int ldgpu_span_offsets_device(ldgpu_ctx* ctx, const int64_t* d_offsets, int64_t n_docs, int32_t width,
+                              int32_t stride, int64_t* d_span_offsets, void* stream);
+
+/* Host buffers in and out; synchronous and thread-safe as ldgpu_score.
+ * out_labels [n_spans], out_scores nullable [n_spans][n_langs], n_spans =
+ * span_offsets[n_docs] of ldgpu_span_offsets.  Argument checks, LDGPU_EROWLEN
+ * (raised when a window inside some span hits a wrong-length row) and the
+ * pipeline over pinned / pageable buffers are those of ldgpu_score -- except
+ * the document-length limit: only spans are scored, so a document may have
+ * 2^28 bytes and more.  Only the documents' bytes cross to the device, never
+ * the width / stride expansion. */
+int ldgpu_score_spans(ldgpu_model* model, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs,
+                      int32_t width, int32_t stride, int32_t* out_labels, double* out_scores);
+
+/* Device-resident variant, asynchronous on `stream` under the rules of
+ * ldgpu_score_device (d_bytes 4-byte aligned, n_bytes >= d_offsets[n_docs],
+ * offsets trusted; documents of any length).  d_span_offsets [n_docs + 1] is
+ * ldgpu_span_offsets_device's output for the same width and stride, n_spans
+ * its last entry (which the caller knows, or bounds: a span index at or
+ * beyond d_span_offsets[n_docs] is scored as an empty span, label 0).
+ * d_labels [n_spans], d_scores nullable [n_spans][n_langs].  The spans are
+ * gathered in chunks (at most 64 MiB of span bytes, 2^20 spans) into
+ * stream-ordered scratch and scored from there; nothing is read back. */
+int ldgpu_score_spans_device(ldgpu_model* model, const uint8_t* d_bytes, int64_t n_bytes,
+                             const int64_t* d_offsets, int64_t n_docs, int32_t width, int32_t stride,
+                             const int64_t* d_span_offsets, int64_t n_spans,
+                             int32_t* d_labels, double* d_scores, void* stream);
+
 /* -------------------------------------------------------------------- FIT */
 typedef struct ldgpu_counts ldgpu_counts;
 

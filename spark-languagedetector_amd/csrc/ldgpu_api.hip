@@ -2189,6 +2189,281 @@ int score_host(ldgpu_model* m, ScorePipe* pp, const uint8_t* bytes, const int64_
 }
 }  // namespace
 
+// ------------------------------------------------------------- SCORE: spans
+// Overlapping spans of `width` bytes every `stride` bytes, cut on the device
+// and scored as documents of their own (the rule: include/ldgpu.h; the
+// kernels: ldgpu_spans.hip).
+namespace {
+// A chunk holds as many spans as fit this many gathered bytes (at least one),
+// at most kSpanChunkMax: the host cuts span ranges from n_spans and width
+// alone, nothing is read back.
+constexpr int64_t kSpanChunkBytes = 64ll << 20;
+constexpr int64_t kSpanChunkMax = 1ll << 20;
+int64_t span_chunk_spans(int32_t width) {
+    // (tests: chunks of a few spans, cutting inside documents)
+    if (const char* c = diag_env("LDGPU_SPAN_CHUNK_SPANS")) return std::max<int64_t>(1, atoll(c));
+    return std::min(kSpanChunkMax, std::max<int64_t>(1, kSpanChunkBytes / width));
+}
+int check_span_args(int32_t width, int32_t stride) {
+    if (width < 1) return fail(LDGPU_EINVAL, "span width = %d < 1", width);
+    if (stride < 1 || stride > width)
+        return fail(LDGPU_EINVAL, "span stride = %d outside [1, width = %d]", stride, width);
+    if (width >= kMaxDocBytes)
+        return fail(LDGPU_EUNSUPPORTED, "span width = %d: the device path's limit is %lld", width,
+                    (long long)kMaxDocBytes - 1);
+    return LDGPU_OK;
+}
+int64_t span_count(int64_t len, int64_t width, int64_t stride) {
+    return len <= width ? 1 : 1 + (len - width + stride - 1) / stride;
+}
+size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// One chunk -- the spans [sp.g0, sp.g0 + sp.nc) of the corpus sp describes --
+// gathered into stream-ordered scratch and scored from there: labels to
+// d_labels [nc], scores to d_scores (nullable) [nc][L].  The gathered bytes
+// are 4-byte aligned and followed by 16 spare bytes, as the host pipeline's
+// stage buffer is.
+int span_chunk(ldgpu_model* m, SpanParams sp, int32_t* d_labels, double* d_scores, int32_t* d_err, hipStream_t st) {
+    const int64_t nc = sp.nc;
+    size_t scan_bytes = 0;
+    HIP_TRY(span_scan_bytes(nc + 1, &scan_bytes));
+    const size_t n_src = up256(sizeof(int64_t) * (size_t)nc), n_len = up256(sizeof(int64_t) * (size_t)(nc + 1));
+    const size_t n_scan = up256(scan_bytes);
+    const size_t n_out = (((size_t)nc * (size_t)sp.width + 3) & ~(size_t)3) + 16;
+    char* scratch = nullptr;
+    HIP_TRY(hipMallocAsync((void**)&scratch, n_src + 2 * n_len + n_scan + n_out, st));
+    sp.src = (int64_t*)scratch;
+    sp.len = (int64_t*)(scratch + n_src);
+    sp.coff = (int64_t*)(scratch + n_src + n_len);
+    void* scan_tmp = scratch + n_src + 2 * n_len;
+    sp.out = (uint8_t*)(scratch + n_src + 2 * n_len + n_scan);
+    const hipError_t e = launch_span_gather(sp, scan_tmp, scan_bytes, m->ctx->cus, st);
+    int rc = LDGPU_OK;
+    if (e == hipSuccess) rc = score_launch(m, sp.out, (int64_t)n_out, sp.coff, nc, d_labels, d_scores, d_err, st);
+    (void)hipFreeAsync(scratch, st);
+    HIP_TRY(e);
+    return rc;
+}
+}  // namespace
+
+extern "C" int ldgpu_span_offsets(const int64_t* offsets, int64_t n_docs, int32_t width, int32_t stride,
+                                  int64_t* span_offsets) {
+    if (int rc = check_offsets(offsets, n_docs)) return rc;
+    if (int rc = check_span_args(width, stride)) return rc;
+    if (!span_offsets) return fail(LDGPU_EINVAL, "span_offsets is NULL");
+    int64_t g = 0;
+    for (int64_t d = 0; d < n_docs; ++d) {
+        span_offsets[d] = g;
+        g += span_count(offsets[d + 1] - offsets[d], width, stride);
+    }
+    span_offsets[n_docs] = g;
+    return ok();
+}
+
+extern "C" int ldgpu_span_offsets_device(ldgpu_ctx* ctx, const int64_t* d_offsets, int64_t n_docs, int32_t width,
+                                         int32_t stride, int64_t* d_span_offsets, void* stream) {
+    if (!ctx) return fail(LDGPU_EINVAL, "context is NULL");
+    if (n_docs < 0) return fail(LDGPU_EINVAL, "n_docs < 0");
+    if (int rc = check_span_args(width, stride)) return rc;
+    if (!d_span_offsets || (n_docs > 0 && !d_offsets)) return fail(LDGPU_EINVAL, "device pointer is NULL");
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(ctx->device));
+    size_t scan_bytes = 0;
+    HIP_TRY(span_scan_bytes(n_docs + 1, &scan_bytes));
+    const size_t n_cnt = up256(sizeof(int64_t) * (size_t)(n_docs + 1));
+    char* scratch = nullptr;
+    HIP_TRY(hipMallocAsync((void**)&scratch, n_cnt + up256(scan_bytes), st));
+    const hipError_t e = launch_span_offsets(d_offsets, n_docs, width, stride, (int64_t*)scratch, d_span_offsets,
+                                             scratch + n_cnt, scan_bytes, ctx->cus, st);
+    (void)hipFreeAsync(scratch, st);
+    HIP_TRY(e);
+    return ok();
+}
+
+// Chunks of spans gathered and scored one after the other on `stream`; the
+// labels and scores of a chunk go straight to the caller's arrays.
+extern "C" int ldgpu_score_spans_device(ldgpu_model* m, const uint8_t* d_bytes, int64_t n_bytes,
+                                        const int64_t* d_offsets, int64_t n_docs, int32_t width, int32_t stride,
+                                        const int64_t* d_span_offsets, int64_t n_spans, int32_t* d_labels,
+                                        double* d_scores, void* stream) {
+    if (!m) return fail(LDGPU_EINVAL, "model is NULL");
+    if (n_docs < 0) return fail(LDGPU_EINVAL, "n_docs < 0");
+    if (n_spans < 0) return fail(LDGPU_EINVAL, "n_spans < 0");
+    if (int rc = check_span_args(width, stride)) return rc;
+    if (n_spans > 0 && (!d_offsets || !d_span_offsets || !d_labels || (n_bytes > 0 && !d_bytes)))
+        return fail(LDGPU_EINVAL, "device pointer is NULL");
+    if (((uintptr_t)d_bytes & 3) != 0) return fail(LDGPU_EINVAL, "d_bytes must be 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    const int64_t chunk = span_chunk_spans(width);
+    for (int64_t g0 = 0; g0 < n_spans; g0 += chunk) {
+        SpanParams sp{};
+        sp.bytes = d_bytes;
+        sp.n_bytes = n_bytes;
+        sp.offsets = d_offsets;
+        sp.n_docs = n_docs;
+        sp.span_offsets = d_span_offsets;
+        sp.width = width;
+        sp.stride = stride;
+        sp.g0 = g0;
+        sp.nc = std::min(chunk, n_spans - g0);
+        if (int rc = span_chunk(m, sp, d_labels + g0, d_scores ? d_scores + g0 * m->L : nullptr, m->d_err, st))
+            return rc;
+    }
+    if (m->has_bad && n_spans > 0) {
+        if (int rc = check_row_error(m, m->d_err, st)) return rc;
+    }
+    return ok();
+}
+
+namespace {
+int score_spans_host(ldgpu_model* m, ScorePipe* pp, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs,
+                     const std::vector<int64_t>& soff, int32_t width, int32_t stride, int32_t* out_labels,
+                     double* out_scores) {
+    // score_host's two-stage pipeline over chunks of spans.  Per chunk the host
+    // copies in the source byte range its spans touch -- from the first span's
+    // first byte to the last span's end: the documents' bytes once, never the
+    // width / stride expansion -- with the chunk's view of the offsets: the
+    // documents' offsets relative to that range (the first document's may be
+    // negative: the chunk starts at one of its later spans) and their span
+    // offsets relative to the chunk's first span.
+    // (With scores the stage's score buffer bounds a chunk too, as in the top-k form.)
+    int64_t chunk = span_chunk_spans(width);
+    if (out_scores) chunk = std::min(chunk, topk_chunk_docs(m->L));
+    const int64_t n_spans = soff[n_docs];
+    const bool pinned_in = nb_total_pinned(bytes, offsets, n_docs);
+    const bool pinned_out = is_pinned(out_labels) && (!out_scores || is_pinned(out_scores));
+    auto retire = [&](ScoreStage& st) -> int {
+        if (!st.busy) return LDGPU_OK;
+        HIP_TRY(hipEventSynchronize(st.done));
+        st.busy = false;
+        if (!pinned_out) {
+            memcpy(out_labels + st.d0, st.h_labels.p, sizeof(int32_t) * st.nd);
+            if (out_scores) par_memcpy(out_scores + st.d0 * m->L, st.h_scores.p, sizeof(double) * st.nd * m->L);
+        }
+        return LDGPU_OK;
+    };
+    // the last document d with soff[d] <= g
+    auto doc_of = [&](int64_t g) -> int64_t {
+        return (int64_t)(std::upper_bound(soff.begin(), soff.begin() + n_docs, g) - soff.begin()) - 1;
+    };
+    auto issue = [&](ScoreStage& st, int64_t g0, int64_t g1) -> int {
+        const int64_t nc = g1 - g0, dA = doc_of(g0), dB = doc_of(g1 - 1), ndc = dB - dA + 1;
+        const int64_t lo = offsets[dA] + (g0 - soff[dA]) * stride;
+        const int64_t hi = offsets[dB] + std::min<int64_t>((g1 - 1 - soff[dB]) * stride + width,
+                                                           offsets[dB + 1] - offsets[dB]);
+        const int64_t nb = hi - lo;
+        HIP_TRY(st.bytes.ensure((size_t)nb + 16));
+        HIP_TRY(st.offsets.ensure(2 * sizeof(int64_t) * (ndc + 1)));
+        HIP_TRY(st.labels.ensure(sizeof(int32_t) * nc));
+        if (out_scores) HIP_TRY(st.scores.ensure(sizeof(double) * nc * m->L));
+        HIP_TRY(st.h_offsets.ensure(2 * sizeof(int64_t) * (ndc + 1)));
+        int64_t* ho = (int64_t*)st.h_offsets.p;
+        int64_t* hs = ho + ndc + 1;
+        for (int64_t i = 0; i <= ndc; ++i) {
+            ho[i] = offsets[dA + i] - lo;
+            hs[i] = soff[dA + i] - g0;
+        }
+        const uint8_t* src = bytes + lo;
+        if (nb && !pinned_in) {
+            HIP_TRY(st.h_bytes.ensure((size_t)nb));
+            par_memcpy(st.h_bytes.p, src, (size_t)nb);
+            src = (const uint8_t*)st.h_bytes.p;
+        }
+        if (nb) HIP_TRY(hipMemcpyAsync(st.bytes.p, src, nb, hipMemcpyHostToDevice, st.stream));
+        HIP_TRY(hipMemcpyAsync(st.offsets.p, ho, 2 * sizeof(int64_t) * (ndc + 1), hipMemcpyHostToDevice, st.stream));
+        SpanParams sp{};
+        sp.bytes = (const uint8_t*)st.bytes.p;
+        sp.n_bytes = nb;
+        sp.offsets = (const int64_t*)st.offsets.p;
+        sp.n_docs = ndc;
+        sp.span_offsets = sp.offsets + ndc + 1;
+        sp.width = width;
+        sp.stride = stride;
+        sp.g0 = 0;
+        sp.nc = nc;
+        if (int r = span_chunk(m, sp, (int32_t*)st.labels.p, out_scores ? (double*)st.scores.p : nullptr, pp->d_err,
+                               st.stream))
+            return r;
+        int32_t* lab_dst = out_labels + g0;
+        double* sc_dst = out_scores ? out_scores + g0 * m->L : nullptr;
+        if (!pinned_out) {
+            HIP_TRY(st.h_labels.ensure(sizeof(int32_t) * nc));
+            lab_dst = (int32_t*)st.h_labels.p;
+            if (out_scores) {
+                HIP_TRY(st.h_scores.ensure(sizeof(double) * nc * m->L));
+                sc_dst = (double*)st.h_scores.p;
+            }
+        }
+        HIP_TRY(hipMemcpyAsync(lab_dst, st.labels.p, sizeof(int32_t) * nc, hipMemcpyDeviceToHost, st.stream));
+        if (out_scores)
+            HIP_TRY(hipMemcpyAsync(sc_dst, st.scores.p, sizeof(double) * nc * m->L, hipMemcpyDeviceToHost,
+                                   st.stream));
+        HIP_TRY(hipEventRecord(st.done, st.stream));
+        st.d0 = g0;
+        st.nd = nc;
+        st.busy = true;
+        return LDGPU_OK;
+    };
+    int k = 0;
+    int rc = LDGPU_OK;
+    for (int64_t g0 = 0; g0 < n_spans; g0 += chunk, ++k) {
+        ScoreStage& st = pp->stage[k & 1];
+        if ((rc = retire(st))) break;
+        if ((rc = issue(st, g0, std::min(n_spans, g0 + chunk)))) break;
+    }
+    // drain as score_host does: every queued copy completes before the call
+    // returns, also after an error
+    for (auto& st : pp->stage) {
+        const hipError_t e = hipStreamSynchronize(st.stream);
+        if (!rc && e != hipSuccess) rc = fail(LDGPU_EDEVICE, "score pipeline: %s", hipGetErrorString(e));
+    }
+    for (int i = 0; i < 2; ++i) {
+        ScoreStage& st = pp->stage[(k + i) & 1];
+        if (rc) {
+            st.busy = false;  // the call failed: its outputs are undefined
+            continue;
+        }
+        rc = retire(st);
+    }
+    if (rc) {
+        (void)hipMemset(pp->d_err, 0, sizeof(int32_t));  // no stale row error for the pipeline's next call
+        return rc;
+    }
+    if (m->has_bad) {
+        if (int r = check_row_error(m, pp->d_err, pp->stage[0].stream)) return r;
+    }
+    return LDGPU_OK;
+}
+}  // namespace
+
+// Thread-safe and concurrent like ldgpu_score: a pipeline of the context's pool.
+extern "C" int ldgpu_score_spans(ldgpu_model* m, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs,
+                                 int32_t width, int32_t stride, int32_t* out_labels, double* out_scores) {
+    if (!m) return fail(LDGPU_EINVAL, "model is NULL");
+    if (int rc = check_offsets(offsets, n_docs)) return rc;
+    if (int rc = check_span_args(width, stride)) return rc;
+    if (n_docs == 0) return ok();
+    if (!out_labels) return fail(LDGPU_EINVAL, "out_labels is NULL");
+    if (!bytes && offsets[n_docs] > offsets[0]) return fail(LDGPU_EINVAL, "bytes is NULL");
+    // (no document-length limit: only spans are scored, and width is below it)
+    std::vector<int64_t> soff((size_t)n_docs + 1);
+    int64_t g = 0;
+    for (int64_t d = 0; d < n_docs; ++d) {
+        soff[d] = g;
+        g += span_count(offsets[d + 1] - offsets[d], width, stride);
+    }
+    soff[n_docs] = g;
+    ldgpu_ctx* c = m->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    ScorePipe* pp = pipe_acquire(c);
+    if (!pp) return LDGPU_EDEVICE;
+    const int rc = score_spans_host(m, pp, bytes, offsets, n_docs, soff, width, stride, out_labels, out_scores);
+    pipe_release(c, pp);
+    if (rc) return rc;
+    return ok();
+}
+
 // ---------------------------------------------------------------------- FIT
 struct ldgpu_counts {
     ldgpu_ctx* ctx = nullptr;

@@ -241,6 +241,29 @@ struct TopkParams {
 constexpr int kMaxTopk = 16;          // LDGPU_MAX_TOPK
 constexpr int kTopkMaxLangs = 4096;   // LDGPU_MAX_LANGS
 hipError_t launch_topk(const TopkParams& p, int cus, hipStream_t stream);
+// Span scoring (ldgpu_spans.hip; the span rule of ldgpu_score_spans,
+// include/ldgpu.h): the spans [g0, g0 + nc) of a corpus gathered into a packed
+// corpus of their own (out, coff) that score_launch then scores.
+struct SpanParams {
+    const uint8_t* bytes;         // the caller's documents
+    int64_t n_bytes;              // readable bytes of `bytes`
+    const int64_t* offsets;       // [n_docs + 1]
+    int64_t n_docs;
+    const int64_t* span_offsets;  // [n_docs + 1]: first span of every document
+    int32_t width, stride;
+    int64_t g0, nc;               // the chunk's spans
+    int64_t* src;                 // out [nc]: a span's first byte in `bytes`
+    int64_t* len;                 // out [nc + 1]: its length (len[nc] = 0)
+    int64_t* coff;                // out [nc + 1]: its first byte in `out` (the scan of len)
+    uint8_t* out;                 // out: the spans' bytes, nc width at the most
+};
+// scratch bytes of the exclusive scans over n_items int64 (hipcub)
+hipError_t span_scan_bytes(int64_t n_items, size_t* bytes);
+// span_offsets [n_docs + 1] from offsets; cnt: [n_docs + 1] scratch
+hipError_t launch_span_offsets(const int64_t* offsets, int64_t n_docs, int32_t width, int32_t stride, int64_t* cnt,
+                               int64_t* span_offsets, void* scan_tmp, size_t scan_bytes, int cus, hipStream_t stream);
+// geometry (src, len), the scan into coff, the gather into out
+hipError_t launch_span_gather(const SpanParams& p, void* scan_tmp, size_t scan_bytes, int cus, hipStream_t stream);
 // sets the dynamic-LDS limit and returns the resident workgroups per CU
 // (chunks: a count-mode table's keyed bloom in the chunk layout)
 hipError_t score_prepare(int slices, int mode, bool lds_bloom, bool chunks, size_t lds_bytes, int* blocks_per_cu);

@@ -25,7 +25,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import encoding
+from . import encoding, spans
 from .runtime import DeviceCounts, DeviceModel
 
 
@@ -167,6 +167,42 @@ class LanguageDetectorModel(_Params):
         out = df.copy()
         out[candidatesCol] = pd.Series(langs, index=out.index, dtype=object)
         out[scoresCol] = pd.Series([row.tolist() for row in scores], index=out.index, dtype=object)
+        return out
+
+    # Per-span output for mixed-language text (an addition: the reference
+    # labels the whole document).  The span and run rules: languagedetection.spans.
+    def predict_spans(self, texts: Sequence[str], width: int, stride: int) -> List[List[Tuple[int, int, str]]]:
+        """Per text its runs (start, end, language): spans of `width` units
+        every `stride` units labelled on the GPU, consecutive spans of one
+        language merged; start / end index the text's UTF-16 units."""
+        for t in texts:
+            if t is None:
+                raise NullPointerException("text is null")
+        data, offsets = encoding.pack_score(texts)
+        labels, _, soff = self.device_model().score_spans(data, offsets, width, stride)
+        out = []
+        for d in range(len(texts)):
+            r = spans.runs(int(offsets[d + 1] - offsets[d]), labels[soff[d]:soff[d + 1]], width, stride)
+            out.append([(a, b, self.supportedLanguages[lab]) for a, b, lab in r])
+        return out
+
+    def transformSpans(self, dataset, width: int, stride: int, outputCol: str = "langSpans"):
+        """Append outputCol (the row's runs as a list of (start, end, language));
+        an existing column of that name is rejected as transformSchema rejects
+        outputCol."""
+        import pandas as pd
+        df = dataset if isinstance(dataset, pd.DataFrame) else pd.DataFrame(dataset)
+        schema = self._schema_of(df)
+        in_type = schema.get(self.getInputCol())
+        if in_type is None:
+            raise ValueError(f"Field \"{self.getInputCol()}\" does not exist.")
+        if in_type != "string":
+            raise ValueError(f"requirement failed: Input type must be StringType but got {in_type}.")
+        if outputCol in schema:
+            raise ValueError(f"requirement failed: Column {outputCol} already exists.")
+        found = self.predict_spans(list(df[self.getInputCol()]), width, stride)
+        out = df.copy()
+        out[outputCol] = pd.Series(found, index=out.index, dtype=object)
         return out
 
     # persistence (LanguageDetectorModel.scala:24-105): the reference's layout

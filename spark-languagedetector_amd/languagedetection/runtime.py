@@ -178,6 +178,57 @@ class DeviceModel(_Owner):
                                                      ctypes.c_void_p(d_top_scores) if d_top_scores else None,
                                                      ctypes.c_void_p(st) if st else None))
 
+    # Span scoring (an addition; the rule: languagedetection.spans)
+    def span_offsets(self, offsets: np.ndarray, width: int, stride: int) -> np.ndarray:
+        """int64[n_docs + 1]: every document's first span (ldgpu_span_offsets: host arithmetic)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        out = np.zeros(max(len(offsets), 1), dtype=np.int64)
+        self._check(self.lib.ldgpu_span_offsets(_ptr(offsets), len(offsets) - 1, int(width), int(stride), _ptr(out)))
+        return out
+
+    def span_offsets_device(self, d_offsets: int, n_docs: int, width: int, stride: int, d_span_offsets: int,
+                            stream: Optional[int] = None) -> None:
+        """Device pointers -> d_span_offsets int64[n_docs + 1] in place, async
+        on `stream` as score_device (ldgpu_span_offsets_device)."""
+        st = self.stream() if stream is None else stream
+        self._check(self.lib.ldgpu_span_offsets_device(self.ctx, ctypes.c_void_p(d_offsets), n_docs, int(width),
+                                                       int(stride), ctypes.c_void_p(d_span_offsets),
+                                                       ctypes.c_void_p(st) if st else None))
+
+    def score_spans(self, data: np.ndarray, offsets: np.ndarray, width: int, stride: int, want_scores: bool = False,
+                    out_labels: Optional[np.ndarray] = None, out_scores: Optional[np.ndarray] = None
+                    ) -> Tuple[np.ndarray, Optional[np.ndarray], np.ndarray]:
+        """Host buffers -> (labels int32[n_spans], scores fp64[n_spans, L] or
+        None, span_offsets int64[n_docs + 1]): every span of `width` bytes
+        every `stride` bytes scored as a document of its own
+        (ldgpu_score_spans).  `out_labels` / `out_scores` (e.g. PinnedArray
+        arrays) receive the results."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        soff = self.span_offsets(offsets, width, stride)
+        n = int(soff[-1])
+        labels = np.zeros(n, dtype=np.int32) if out_labels is None else out_labels
+        scores = (np.zeros((n, self.L), dtype=np.float64) if out_scores is None else out_scores) if want_scores else None
+        assert labels.dtype == np.int32 and labels.shape == (n,) and labels.flags.c_contiguous
+        assert scores is None or (scores.dtype == np.float64 and scores.shape == (n, self.L)
+                                  and scores.flags.c_contiguous)
+        self._check(self.lib.ldgpu_score_spans(self.h, _ptr(data), _ptr(offsets), len(offsets) - 1, int(width),
+                                               int(stride), _ptr(labels), _ptr(scores)))
+        return labels, scores, soff
+
+    def score_spans_device(self, d_bytes: int, n_bytes: int, d_offsets: int, n_docs: int, width: int, stride: int,
+                           d_span_offsets: int, n_spans: int, d_labels: int, d_scores: int = 0,
+                           stream: Optional[int] = None) -> None:
+        """Device pointers -> the [n_spans] labels (and [n_spans, L] scores) in
+        place, async on `stream` as score_device (ldgpu_score_spans_device)."""
+        st = self.stream() if stream is None else stream
+        self._check(self.lib.ldgpu_score_spans_device(self.h, ctypes.c_void_p(d_bytes), n_bytes,
+                                                      ctypes.c_void_p(d_offsets), n_docs, int(width), int(stride),
+                                                      ctypes.c_void_p(d_span_offsets), n_spans,
+                                                      ctypes.c_void_p(d_labels),
+                                                      ctypes.c_void_p(d_scores) if d_scores else None,
+                                                      ctypes.c_void_p(st) if st else None))
+
 
 class DeviceCounts(_Owner):
     """A (gram, language) -> count table on one GPU (computeGrams + reduceGrams)."""
