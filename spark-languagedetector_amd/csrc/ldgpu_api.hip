@@ -230,24 +230,34 @@ int check_offsets(const int64_t* off, int64_t n_docs) {
     return LDGPU_OK;
 }
 
+// The greedy chunk cut of the host-buffer calls: the end d1 of the chunk that
+// starts at document d0 -- documents while they number at most max_docs and
+// their bytes at most max_bytes, one document at least.
+int64_t chunk_end(const int64_t* offsets, int64_t n_docs, int64_t d0, int64_t max_docs, int64_t max_bytes) {
+    int64_t d1 = d0 + 1;
+    while (d1 < n_docs && d1 - d0 < max_docs && offsets[d1 + 1] - offsets[d0] <= max_bytes) ++d1;
+    return d1;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------ context
-// one stage of the host-buffer scoring pipeline (ldgpu_score): pinned
+// one stage of the host-buffer scoring pipeline (run_score_pipe): pinned
 // staging + device buffers of one chunk, on its own stream
 struct ScoreStage {
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
     DevBuf bytes, offsets, labels, scores;
+    // pinned staging of the inputs and of a call's two output arrays
     HostBuf h_bytes, h_offsets, h_labels, h_scores;
     // top-k calls (ldgpu_score_topk): the chunk's [nd][k] labels and scores
+    // (`labels` and `scores` are then the scratch they are selected from)
     DevBuf top_labels, top_scores;
-    HostBuf h_top_labels, h_top_scores;
-    int64_t d0 = 0, nd = 0;
+    int64_t d0 = 0, nd = 0;  // the chunk in flight: its first item and their number
     bool busy = false;
 };
 
-// One ldgpu_score call's pipeline: two stages plus the call's own error word
+// One host scoring call's pipeline: two stages plus the call's own error word
 // (a wrong-length row hit by THIS call's documents).  Contexts keep a pool:
 // concurrent callers (Spark task threads of one executor, Spark.scala:11
 // local[4]) each take a pipeline and run on their own streams.
@@ -344,8 +354,7 @@ void pipe_destroy(ScorePipe* pp) {
     for (auto& st : pp->stage) {
         if (st.stream) (void)hipStreamSynchronize(st.stream);
         for (DevBuf* b : {&st.bytes, &st.offsets, &st.labels, &st.scores, &st.top_labels, &st.top_scores}) b->release();
-        for (HostBuf* b : {&st.h_bytes, &st.h_offsets, &st.h_labels, &st.h_scores, &st.h_top_labels, &st.h_top_scores})
-            b->release();
+        for (HostBuf* b : {&st.h_bytes, &st.h_offsets, &st.h_labels, &st.h_scores}) b->release();
         if (st.done) (void)hipEventDestroy(st.done);
         if (st.stream) (void)hipStreamDestroy(st.stream);
     }
@@ -1884,7 +1893,10 @@ bool nb_total_pinned(const uint8_t* bytes, const int64_t* offsets, int64_t n_doc
     return is_pinned(bytes + offsets[0]) && is_pinned(bytes + offsets[n_docs] - 1);
 }
 
+// after a call's launches: its error word read back on st, when the model has
+// a wrong-length row at all
 int check_row_error(ldgpu_model* m, int32_t* d_err, hipStream_t st) {
+    if (!m->has_bad) return LDGPU_OK;
     int32_t err = 0;
     HIP_TRY(hipMemcpyAsync(&err, d_err, sizeof err, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -1899,21 +1911,31 @@ int check_row_error(ldgpu_model* m, int32_t* d_err, hipStream_t st) {
     }
     return LDGPU_OK;
 }
+
+// The start of a device-pointer scoring call: the checks the three entry
+// points share, in their order -- the model, n_docs, the call's own arguments
+// (`own`, run once the model is known), a missing pointer (`null_ptr`, worked
+// out by the caller), d_bytes' alignment -- then the model's device made current.
+template <class Own>
+int device_call_begin(const ldgpu_model* m, int64_t n_docs, const void* d_bytes, bool null_ptr, Own own) {
+    if (!m) return fail(LDGPU_EINVAL, "model is NULL");
+    if (n_docs < 0) return fail(LDGPU_EINVAL, "n_docs < 0");
+    if (int rc = own()) return rc;
+    if (null_ptr) return fail(LDGPU_EINVAL, "device pointer is NULL");
+    if (((uintptr_t)d_bytes & 3) != 0) return fail(LDGPU_EINVAL, "d_bytes must be 4-byte aligned");
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    return LDGPU_OK;
+}
+const auto no_own_checks = [] { return (int)LDGPU_OK; };
 }  // namespace
 
 extern "C" int ldgpu_score_device(ldgpu_model* m, const uint8_t* d_bytes, int64_t n_bytes, const int64_t* d_offsets,
                                   int64_t n_docs, int32_t* d_labels, double* d_scores, void* stream) {
-    if (!m) return fail(LDGPU_EINVAL, "model is NULL");
-    if (n_docs < 0) return fail(LDGPU_EINVAL, "n_docs < 0");
-    if (n_docs > 0 && (!d_offsets || !d_labels || (n_bytes > 0 && !d_bytes)))
-        return fail(LDGPU_EINVAL, "device pointer is NULL");
-    if (((uintptr_t)d_bytes & 3) != 0) return fail(LDGPU_EINVAL, "d_bytes must be 4-byte aligned");
+    const bool null_ptr = n_docs > 0 && (!d_offsets || !d_labels || (n_bytes > 0 && !d_bytes));
+    if (int rc = device_call_begin(m, n_docs, d_bytes, null_ptr, no_own_checks)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipSetDevice(m->ctx->device));
     if (int rc = score_launch(m, d_bytes, n_bytes, d_offsets, n_docs, d_labels, d_scores, m->d_err, st)) return rc;
-    if (m->has_bad) {
-        if (int rc = check_row_error(m, m->d_err, st)) return rc;
-    }
+    if (int rc = check_row_error(m, m->d_err, st)) return rc;
     return ok();
 }
 
@@ -1932,6 +1954,20 @@ int check_topk(const ldgpu_model* m, int32_t k) {
         return fail(LDGPU_EINVAL, "k = %d outside [1, min(n_langs = %d, %d)]", k, m->L, LDGPU_MAX_TOPK);
     return LDGPU_OK;
 }
+// the k best of each of nd score rows ([nd][L]) to top_labels [nd][k] and
+// top_scores (nullable) [nd][k]
+hipError_t topk_select(const ldgpu_model* m, const double* scores, int64_t nd, int32_t k, int32_t* top_labels,
+                       double* top_scores, hipStream_t st) {
+    TopkParams t{};
+    t.scores = scores;
+    t.stride = m->L;
+    t.n = nd;
+    t.L = m->L;
+    t.k = k;
+    t.top_labels = top_labels;
+    t.top_scores = top_scores;
+    return launch_topk(t, m->ctx->cus, st);
+}
 }  // namespace
 
 // Chunks of documents (sub-ranges of d_offsets, whose entries are absolute into
@@ -1940,14 +1976,9 @@ int check_topk(const ldgpu_model* m, int32_t k) {
 extern "C" int ldgpu_score_topk_device(ldgpu_model* m, const uint8_t* d_bytes, int64_t n_bytes,
                                        const int64_t* d_offsets, int64_t n_docs, int32_t k, int32_t* d_top_labels,
                                        double* d_top_scores, void* stream) {
-    if (!m) return fail(LDGPU_EINVAL, "model is NULL");
-    if (n_docs < 0) return fail(LDGPU_EINVAL, "n_docs < 0");
-    if (int rc = check_topk(m, k)) return rc;
-    if (n_docs > 0 && (!d_offsets || !d_top_labels || (n_bytes > 0 && !d_bytes)))
-        return fail(LDGPU_EINVAL, "device pointer is NULL");
-    if (((uintptr_t)d_bytes & 3) != 0) return fail(LDGPU_EINVAL, "d_bytes must be 4-byte aligned");
+    const bool null_ptr = n_docs > 0 && (!d_offsets || !d_top_labels || (n_bytes > 0 && !d_bytes));
+    if (int rc = device_call_begin(m, n_docs, d_bytes, null_ptr, [&] { return check_topk(m, k); })) return rc;
     hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipSetDevice(m->ctx->device));
     const int64_t chunk = topk_chunk_docs(m->L);
     for (int64_t d0 = 0; d0 < n_docs; d0 += chunk) {
         const int64_t nd = std::min(chunk, n_docs - d0);
@@ -1957,209 +1988,140 @@ extern "C" int ldgpu_score_topk_device(ldgpu_model* m, const uint8_t* d_bytes, i
         double* sc = (double*)scratch;
         int rc = score_launch(m, d_bytes, n_bytes, d_offsets + d0, nd, (int32_t*)(scratch + score_bytes), sc, m->d_err,
                               st);
-        hipError_t e = hipSuccess;
-        if (!rc) {
-            TopkParams t{};
-            t.scores = sc;
-            t.stride = m->L;
-            t.n = nd;
-            t.L = m->L;
-            t.k = k;
-            t.top_labels = d_top_labels + d0 * k;
-            t.top_scores = d_top_scores ? d_top_scores + d0 * k : nullptr;
-            e = launch_topk(t, m->ctx->cus, st);
-        }
+        const hipError_t e = rc ? hipSuccess
+                                : topk_select(m, sc, nd, k, d_top_labels + d0 * k,
+                                              d_top_scores ? d_top_scores + d0 * k : nullptr, st);
         (void)hipFreeAsync(scratch, st);
         if (rc) return rc;
         HIP_TRY(e);
     }
-    if (m->has_bad && n_docs > 0) {
+    if (n_docs > 0) {
         if (int rc = check_row_error(m, m->d_err, st)) return rc;
     }
     return ok();
 }
 
+// ------------------------------------------------- SCORE: host-buffer calls
+// ldgpu_score, ldgpu_score_topk and ldgpu_score_spans are three forms of one
+// two-stage pipeline (run_score_pipe).  A form is a ScoreCall of plain values
+// plus two callables: `cut`, which names the chunk that starts at an item, and
+// `launch`, which queues the chunk's kernels on its stage.
 namespace {
-// the top-k form's outputs ([n_docs][k]; scores nullable)
-struct TopkOut {
-    int32_t k;
-    int32_t* labels;
-    double* scores;
+// One output array of a call: per item (a document, or a span) `item` bytes
+// that a chunk's launch leaves in the stage's `dev` buffer.  They are copied to
+// the caller's array `base` directly when the call's outputs are pinned, and
+// through the stage's pinned `host` buffer otherwise.
+struct PipeOut {
+    DevBuf ScoreStage::*dev;
+    HostBuf ScoreStage::*host;
+    void* base;  // nullptr: not asked for
+    size_t item;
 };
-int score_host(ldgpu_model* m, ScorePipe* pp, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs,
-               int32_t* out_labels, double* out_scores, const TopkOut* tk = nullptr);
-}  // namespace
 
-// Thread-safe and concurrent: each call scores on a pipeline (two streams,
-// pinned staging, its own error word) taken from the context's pool.
-extern "C" int ldgpu_score(ldgpu_model* m, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs,
-                           int32_t* out_labels, double* out_scores) {
-    if (!m) return fail(LDGPU_EINVAL, "model is NULL");
-    if (int rc = check_offsets(offsets, n_docs)) return rc;
-    if (n_docs == 0) return ok();
-    if (!out_labels) return fail(LDGPU_EINVAL, "out_labels is NULL");
-    if (!bytes && offsets[n_docs] > offsets[0]) return fail(LDGPU_EINVAL, "bytes is NULL");
-    for (int64_t d = 0; d < n_docs; ++d)
-        if (offsets[d + 1] - offsets[d] >= kMaxDocBytes)
-            return fail(LDGPU_EUNSUPPORTED, "document %lld has %lld bytes: the device path's limit is %lld",
-                        (long long)d, (long long)(offsets[d + 1] - offsets[d]), (long long)kMaxDocBytes - 1);
-    ldgpu_ctx* c = m->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    ScorePipe* pp = pipe_acquire(c);
-    if (!pp) return LDGPU_EDEVICE;
-    const int rc = score_host(m, pp, bytes, offsets, n_docs, out_labels, out_scores);
-    pipe_release(c, pp);
-    if (rc) return rc;
-    return ok();
-}
+// A chunk as `cut` describes it: the items [i0, i1), the source bytes
+// [lo, hi) they need, and the documents [doc0, doc0 + n_docs) those bytes
+// belong to.  The stage gets the n_docs + 1 document offsets relative to lo
+// and, in the span form, as many span offsets relative to i0 after them.
+struct PipeChunk {
+    int64_t i0, i1;
+    int64_t lo, hi;
+    int64_t doc0, n_docs;
+};
 
-extern "C" int ldgpu_score_topk(ldgpu_model* m, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs,
-                                int32_t k, int32_t* out_top_labels, double* out_top_scores) {
-    if (!m) return fail(LDGPU_EINVAL, "model is NULL");
-    if (int rc = check_offsets(offsets, n_docs)) return rc;
-    if (int rc = check_topk(m, k)) return rc;
-    if (n_docs == 0) return ok();
-    if (!out_top_labels) return fail(LDGPU_EINVAL, "out_top_labels is NULL");
-    if (!bytes && offsets[n_docs] > offsets[0]) return fail(LDGPU_EINVAL, "bytes is NULL");
-    for (int64_t d = 0; d < n_docs; ++d)
-        if (offsets[d + 1] - offsets[d] >= kMaxDocBytes)
-            return fail(LDGPU_EUNSUPPORTED, "document %lld has %lld bytes: the device path's limit is %lld",
-                        (long long)d, (long long)(offsets[d + 1] - offsets[d]), (long long)kMaxDocBytes - 1);
-    ldgpu_ctx* c = m->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    ScorePipe* pp = pipe_acquire(c);
-    if (!pp) return LDGPU_EDEVICE;
-    const TopkOut tk{k, out_top_labels, out_top_scores};
-    const int rc = score_host(m, pp, bytes, offsets, n_docs, nullptr, nullptr, &tk);
-    pipe_release(c, pp);
-    if (rc) return rc;
-    return ok();
-}
+struct ScoreCall {
+    const uint8_t* bytes;
+    const int64_t* offsets;
+    int64_t n_docs;
+    const int64_t* span_offsets;  // the span form's items: [n_docs + 1], else nullptr
+    int64_t n_items;              // documents, or spans
+    PipeOut out[2];               // [0] labels (memcpy), [1] score rows (par_memcpy)
+};
 
-namespace {
-int score_host(ldgpu_model* m, ScorePipe* pp, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs,
-               int32_t* out_labels, double* out_scores, const TopkOut* tk) {
-    // Two-stage pipeline over chunks of documents, one stream per stage: while
-    // the GPU copies and scores chunk i, the host stages chunk i + 1 into the
-    // other stage's pinned buffers (a caller buffer already in pinned memory is
-    // copied from directly) and hands back the labels of chunk i - 1.
-    // Top-k form (tk): every chunk is scored into the stage's score buffer
-    // (at most kTopkScratchBytes of it), its rows selected on the device
-    // (launch_topk), and only the chunk's [nd][k] labels and scores copied
-    // back; the stage's [nd] labels serve score_launch alone.
-    const int64_t kChunkBytes = 64ll << 20;
-    const int64_t kChunkDocs = tk ? std::min<int64_t>(1ll << 20, topk_chunk_docs(m->L)) : 1ll << 20;
-    const bool pinned_in = nb_total_pinned(bytes, offsets, n_docs);
-    const bool pinned_out = tk ? is_pinned(tk->labels) && (!tk->scores || is_pinned(tk->scores))
-                               : is_pinned(out_labels) && (!out_scores || is_pinned(out_scores));
-    const bool want_scores = out_scores || tk;
+// Two-stage pipeline over chunks of items, one stream per stage: while the GPU
+// copies and scores chunk i, the host stages chunk i + 1 into the other
+// stage's pinned buffers (a caller buffer already in pinned memory is copied
+// from directly) and hands back the outputs of chunk i - 1.  A failed call
+// leaves the pooled pipeline clean: drained, both stages idle, the error word
+// zero.
+template <class Cut, class Launch>
+int run_score_pipe(ldgpu_model* m, ScorePipe* pp, const ScoreCall& c, Cut cut, Launch launch) {
+    const bool pinned_in = nb_total_pinned(c.bytes, c.offsets, c.n_docs);
+    bool pinned_out = true;
+    for (const PipeOut& o : c.out) pinned_out = pinned_out && (!o.base || is_pinned(o.base));
     auto retire = [&](ScoreStage& st) -> int {
         if (!st.busy) return LDGPU_OK;
         HIP_TRY(hipEventSynchronize(st.done));
         st.busy = false;
-        if (tk) {
-            if (!pinned_out) {
-                memcpy(tk->labels + st.d0 * tk->k, st.h_top_labels.p, sizeof(int32_t) * st.nd * tk->k);
-                if (tk->scores) memcpy(tk->scores + st.d0 * tk->k, st.h_top_scores.p, sizeof(double) * st.nd * tk->k);
-            }
-        } else if (!pinned_out) {
-            memcpy(out_labels + st.d0, st.h_labels.p, sizeof(int32_t) * st.nd);
-            if (out_scores) par_memcpy(out_scores + st.d0 * m->L, st.h_scores.p, sizeof(double) * st.nd * m->L);
-        }
+        if (pinned_out) return LDGPU_OK;
+        const PipeOut &lab = c.out[0], &sc = c.out[1];
+        memcpy((char*)lab.base + st.d0 * lab.item, (st.*lab.host).p, lab.item * st.nd);
+        if (sc.base) par_memcpy((char*)sc.base + st.d0 * sc.item, (st.*sc.host).p, sc.item * st.nd);
         return LDGPU_OK;
     };
     // one chunk's copies and launch on stage st; an error returns without
     // leaving the loop's drain behind (the caller breaks, then drains)
-    auto issue = [&](ScoreStage& st, int64_t d0, int64_t d1) -> int {
-        const int64_t nd = d1 - d0, b0 = offsets[d0], nb = offsets[d1] - b0;
+    auto issue = [&](ScoreStage& st, const PipeChunk& ch) -> int {
+        const int64_t n = ch.i1 - ch.i0, nb = ch.hi - ch.lo, nd1 = ch.n_docs + 1;
+        const size_t off_bytes = sizeof(int64_t) * (c.span_offsets ? 2 : 1) * nd1;
         HIP_TRY(st.bytes.ensure((size_t)nb + 16));
-        HIP_TRY(st.offsets.ensure(sizeof(int64_t) * (nd + 1)));
-        HIP_TRY(st.labels.ensure(sizeof(int32_t) * nd));
-        if (want_scores) HIP_TRY(st.scores.ensure(sizeof(double) * nd * m->L));
-        HIP_TRY(st.h_offsets.ensure(sizeof(int64_t) * (nd + 1)));
+        HIP_TRY(st.offsets.ensure(off_bytes));
+        for (const PipeOut& o : c.out)
+            if (o.base) HIP_TRY((st.*o.dev).ensure(o.item * n));
+        HIP_TRY(st.h_offsets.ensure(off_bytes));
+        // (sources and bases in locals: the stores to ho alias nothing the loops read)
         int64_t* ho = (int64_t*)st.h_offsets.p;
-        for (int64_t i = 0; i <= nd; ++i) ho[i] = offsets[d0 + i] - b0;
-        const uint8_t* src = bytes + b0;
+        const int64_t *doc_off = c.offsets + ch.doc0, lo = ch.lo;
+        for (int64_t i = 0; i < nd1; ++i) ho[i] = doc_off[i] - lo;
+        if (c.span_offsets) {
+            const int64_t *span_off = c.span_offsets + ch.doc0, i0 = ch.i0;
+            for (int64_t i = 0; i < nd1; ++i) ho[nd1 + i] = span_off[i] - i0;
+        }
+        const uint8_t* src = c.bytes + ch.lo;
         if (nb && !pinned_in) {
             HIP_TRY(st.h_bytes.ensure((size_t)nb));
             par_memcpy(st.h_bytes.p, src, (size_t)nb);
             src = (const uint8_t*)st.h_bytes.p;
         }
         if (nb) HIP_TRY(hipMemcpyAsync(st.bytes.p, src, nb, hipMemcpyHostToDevice, st.stream));
-        HIP_TRY(hipMemcpyAsync(st.offsets.p, ho, sizeof(int64_t) * (nd + 1), hipMemcpyHostToDevice, st.stream));
+        HIP_TRY(hipMemcpyAsync(st.offsets.p, ho, off_bytes, hipMemcpyHostToDevice, st.stream));
         // (class mode included: its replay of ambiguous documents reads no
         // count back, so the staging of the next chunk still overlaps)
-        if (int r = score_launch(m, (const uint8_t*)st.bytes.p, nb, (const int64_t*)st.offsets.p, nd,
-                                 (int32_t*)st.labels.p, want_scores ? (double*)st.scores.p : nullptr, pp->d_err,
-                                 st.stream))
-            return r;
-        if (tk) {
-            const size_t nl = sizeof(int32_t) * nd * tk->k, ns = sizeof(double) * nd * tk->k;
-            HIP_TRY(st.top_labels.ensure(nl));
-            if (tk->scores) HIP_TRY(st.top_scores.ensure(ns));
-            TopkParams t{};
-            t.scores = (const double*)st.scores.p;
-            t.stride = m->L;
-            t.n = nd;
-            t.L = m->L;
-            t.k = tk->k;
-            t.top_labels = (int32_t*)st.top_labels.p;
-            t.top_scores = tk->scores ? (double*)st.top_scores.p : nullptr;
-            HIP_TRY(launch_topk(t, m->ctx->cus, st.stream));
-            int32_t* tl_dst = tk->labels + d0 * tk->k;
-            double* ts_dst = tk->scores ? tk->scores + d0 * tk->k : nullptr;
+        if (int r = launch(st, ch, pp->d_err)) return r;
+        void* dst[2] = {nullptr, nullptr};
+        for (int i = 0; i < 2; ++i) {
+            const PipeOut& o = c.out[i];
+            if (!o.base) continue;
+            dst[i] = (char*)o.base + ch.i0 * o.item;
             if (!pinned_out) {
-                HIP_TRY(st.h_top_labels.ensure(nl));
-                tl_dst = (int32_t*)st.h_top_labels.p;
-                if (tk->scores) {
-                    HIP_TRY(st.h_top_scores.ensure(ns));
-                    ts_dst = (double*)st.h_top_scores.p;
-                }
-            }
-            HIP_TRY(hipMemcpyAsync(tl_dst, st.top_labels.p, nl, hipMemcpyDeviceToHost, st.stream));
-            if (tk->scores) HIP_TRY(hipMemcpyAsync(ts_dst, st.top_scores.p, ns, hipMemcpyDeviceToHost, st.stream));
-            HIP_TRY(hipEventRecord(st.done, st.stream));
-            st.d0 = d0;
-            st.nd = nd;
-            st.busy = true;
-            return LDGPU_OK;
-        }
-        int32_t* lab_dst = out_labels + d0;
-        double* sc_dst = out_scores ? out_scores + d0 * m->L : nullptr;
-        if (!pinned_out) {
-            HIP_TRY(st.h_labels.ensure(sizeof(int32_t) * nd));
-            lab_dst = (int32_t*)st.h_labels.p;
-            if (out_scores) {
-                HIP_TRY(st.h_scores.ensure(sizeof(double) * nd * m->L));
-                sc_dst = (double*)st.h_scores.p;
+                HIP_TRY((st.*o.host).ensure(o.item * n));
+                dst[i] = (st.*o.host).p;
             }
         }
-        HIP_TRY(hipMemcpyAsync(lab_dst, st.labels.p, sizeof(int32_t) * nd, hipMemcpyDeviceToHost, st.stream));
-        if (out_scores)
-            HIP_TRY(hipMemcpyAsync(sc_dst, st.scores.p, sizeof(double) * nd * m->L, hipMemcpyDeviceToHost,
-                                   st.stream));
+        for (int i = 0; i < 2; ++i)
+            if (dst[i])
+                HIP_TRY(hipMemcpyAsync(dst[i], (st.*c.out[i].dev).p, c.out[i].item * n, hipMemcpyDeviceToHost,
+                                       st.stream));
         HIP_TRY(hipEventRecord(st.done, st.stream));
-        st.d0 = d0;
-        st.nd = nd;
+        st.d0 = ch.i0;
+        st.nd = n;
         st.busy = true;
         return LDGPU_OK;
     };
     // diagnostics build: fail after issuing this many chunks (error-path tests)
     const char* fail_at = diag_env("LDGPU_FAIL_CHUNK");
-    int64_t d0 = 0;
+    int64_t i0 = 0;
     int k = 0;
     int rc = LDGPU_OK;
-    while (d0 < n_docs && rc == LDGPU_OK) {
-        int64_t d1 = d0 + 1;
-        while (d1 < n_docs && d1 - d0 < kChunkDocs && offsets[d1 + 1] - offsets[d0] <= kChunkBytes) ++d1;
+    while (i0 < c.n_items) {
+        const PipeChunk ch = cut(i0);
         ScoreStage& st = pp->stage[k & 1];
         if ((rc = retire(st))) break;
         if (fail_at && k == atoi(fail_at)) {
             rc = fail(LDGPU_EDEVICE, "injected failure at chunk %d (LDGPU_FAIL_CHUNK)", k);
             break;
         }
-        if ((rc = issue(st, d0, d1))) break;
-        d0 = d1;
+        if ((rc = issue(st, ch))) break;
+        i0 = ch.i1;
         ++k;
     }
     // drain: every copy this call queued (also a half-issued chunk's, after an
@@ -2181,13 +2143,105 @@ int score_host(ldgpu_model* m, ScorePipe* pp, const uint8_t* bytes, const int64_
         (void)hipMemset(pp->d_err, 0, sizeof(int32_t));  // no stale row error for the pipeline's next call
         return rc;
     }
-    if (m->has_bad) {
-        for (auto& st : pp->stage) HIP_TRY(hipStreamSynchronize(st.stream));
-        if (int r = check_row_error(m, pp->d_err, pp->stage[0].stream)) return r;
-    }
+    return check_row_error(m, pp->d_err, pp->stage[0].stream);
+}
+
+// The checks the three host-buffer entry points share, in their order: the
+// model, the offsets, the call's own arguments (`own`), then -- with a
+// document at all -- the first output array (`out_name` for the message),
+// the bytes and, unless the call scores spans only, every document's length.
+template <class Own>
+int check_host_call(const ldgpu_model* m, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs,
+                    const void* out, const char* out_name, bool doc_limit, Own own) {
+    if (!m) return fail(LDGPU_EINVAL, "model is NULL");
+    if (int rc = check_offsets(offsets, n_docs)) return rc;
+    if (int rc = own()) return rc;
+    if (n_docs == 0) return LDGPU_OK;
+    if (!out) return fail(LDGPU_EINVAL, "%s is NULL", out_name);
+    if (!bytes && offsets[n_docs] > offsets[0]) return fail(LDGPU_EINVAL, "bytes is NULL");
+    if (!doc_limit) return LDGPU_OK;
+    for (int64_t d = 0; d < n_docs; ++d)
+        if (offsets[d + 1] - offsets[d] >= kMaxDocBytes)
+            return fail(LDGPU_EUNSUPPORTED, "document %lld has %lld bytes: the device path's limit is %lld",
+                        (long long)d, (long long)(offsets[d + 1] - offsets[d]), (long long)kMaxDocBytes - 1);
     return LDGPU_OK;
 }
+
+// run(pipeline) on a pipeline of the model's context: thread-safe and
+// concurrent, each call scores on its own (two streams, pinned staging, its
+// own error word), taken from the context's pool
+template <class Run>
+int with_pipe(ldgpu_model* m, Run run) {
+    ldgpu_ctx* c = m->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    ScorePipe* pp = pipe_acquire(c);
+    if (!pp) return LDGPU_EDEVICE;
+    const int rc = run(pp);
+    pipe_release(c, pp);
+    return rc ? rc : ok();
+}
+
+// The document forms (labels, top-k) cut greedily: at most 64 MiB and 1M
+// documents a chunk.
+constexpr int64_t kScoreChunkBytes = 64ll << 20;
+int64_t score_chunk_docs() {
+    // (tests: chunks of a few documents)
+    if (const char* c = diag_env("LDGPU_SCORE_CHUNK_DOCS")) return std::max<int64_t>(1, atoll(c));
+    return 1ll << 20;
+}
+auto doc_chunks(const int64_t* offsets, int64_t n_docs, int64_t max_docs) {
+    return [=](int64_t d0) {
+        const int64_t d1 = chunk_end(offsets, n_docs, d0, max_docs, kScoreChunkBytes);
+        return PipeChunk{d0, d1, offsets[d0], offsets[d1], d0, d1 - d0};
+    };
+}
 }  // namespace
+
+extern "C" int ldgpu_score(ldgpu_model* m, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs,
+                           int32_t* out_labels, double* out_scores) {
+    if (int rc = check_host_call(m, bytes, offsets, n_docs, out_labels, "out_labels", true, no_own_checks)) return rc;
+    if (n_docs == 0) return ok();
+    const ScoreCall call{bytes, offsets, n_docs, nullptr, n_docs,
+                         {{&ScoreStage::labels, &ScoreStage::h_labels, out_labels, sizeof(int32_t)},
+                          {&ScoreStage::scores, &ScoreStage::h_scores, out_scores, sizeof(double) * m->L}}};
+    auto launch = [&](ScoreStage& st, const PipeChunk& ch, int32_t* d_err) -> int {
+        return score_launch(m, (const uint8_t*)st.bytes.p, ch.hi - ch.lo, (const int64_t*)st.offsets.p, ch.i1 - ch.i0,
+                            (int32_t*)st.labels.p, out_scores ? (double*)st.scores.p : nullptr, d_err, st.stream);
+    };
+    return with_pipe(m, [&](ScorePipe* pp) {
+        return run_score_pipe(m, pp, call, doc_chunks(offsets, n_docs, score_chunk_docs()), launch);
+    });
+}
+
+// Every chunk is scored into the stage's score buffer (at most
+// kTopkScratchBytes of it), its rows selected on the device, and only the
+// chunk's [nd][k] labels and scores copied back; the stage's [nd] labels serve
+// score_launch alone.
+extern "C" int ldgpu_score_topk(ldgpu_model* m, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs,
+                                int32_t k, int32_t* out_top_labels, double* out_top_scores) {
+    if (int rc = check_host_call(m, bytes, offsets, n_docs, out_top_labels, "out_top_labels", true,
+                                 [&] { return check_topk(m, k); }))
+        return rc;
+    if (n_docs == 0) return ok();
+    const ScoreCall call{bytes, offsets, n_docs, nullptr, n_docs,
+                         {{&ScoreStage::top_labels, &ScoreStage::h_labels, out_top_labels, sizeof(int32_t) * k},
+                          {&ScoreStage::top_scores, &ScoreStage::h_scores, out_top_scores, sizeof(double) * k}}};
+    auto launch = [&](ScoreStage& st, const PipeChunk& ch, int32_t* d_err) -> int {
+        const int64_t nd = ch.i1 - ch.i0;
+        HIP_TRY(st.labels.ensure(sizeof(int32_t) * nd));
+        HIP_TRY(st.scores.ensure(sizeof(double) * nd * m->L));
+        if (int r = score_launch(m, (const uint8_t*)st.bytes.p, ch.hi - ch.lo, (const int64_t*)st.offsets.p, nd,
+                                 (int32_t*)st.labels.p, (double*)st.scores.p, d_err, st.stream))
+            return r;
+        HIP_TRY(topk_select(m, (const double*)st.scores.p, nd, k, (int32_t*)st.top_labels.p,
+                            out_top_scores ? (double*)st.top_scores.p : nullptr, st.stream));
+        return LDGPU_OK;
+    };
+    const int64_t max_docs = std::min(score_chunk_docs(), topk_chunk_docs(m->L));
+    return with_pipe(m, [&](ScorePipe* pp) {
+        return run_score_pipe(m, pp, call, doc_chunks(offsets, n_docs, max_docs), launch);
+    });
+}
 
 // ------------------------------------------------------------- SCORE: spans
 // Overlapping spans of `width` bytes every `stride` bytes, cut on the device
@@ -2215,6 +2269,15 @@ int check_span_args(int32_t width, int32_t stride) {
 }
 int64_t span_count(int64_t len, int64_t width, int64_t stride) {
     return len <= width ? 1 : 1 + (len - width + stride - 1) / stride;
+}
+// span_offsets[d] = document d's first span, span_offsets[n_docs] = their number
+void host_span_offsets(const int64_t* offsets, int64_t n_docs, int32_t width, int32_t stride, int64_t* span_offsets) {
+    int64_t g = 0;
+    for (int64_t d = 0; d < n_docs; ++d) {
+        span_offsets[d] = g;
+        g += span_count(offsets[d + 1] - offsets[d], width, stride);
+    }
+    span_offsets[n_docs] = g;
 }
 size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
 
@@ -2251,12 +2314,7 @@ extern "C" int ldgpu_span_offsets(const int64_t* offsets, int64_t n_docs, int32_
     if (int rc = check_offsets(offsets, n_docs)) return rc;
     if (int rc = check_span_args(width, stride)) return rc;
     if (!span_offsets) return fail(LDGPU_EINVAL, "span_offsets is NULL");
-    int64_t g = 0;
-    for (int64_t d = 0; d < n_docs; ++d) {
-        span_offsets[d] = g;
-        g += span_count(offsets[d + 1] - offsets[d], width, stride);
-    }
-    span_offsets[n_docs] = g;
+    host_span_offsets(offsets, n_docs, width, stride, span_offsets);
     return ok();
 }
 
@@ -2286,15 +2344,13 @@ extern "C" int ldgpu_score_spans_device(ldgpu_model* m, const uint8_t* d_bytes, 
                                         const int64_t* d_offsets, int64_t n_docs, int32_t width, int32_t stride,
                                         const int64_t* d_span_offsets, int64_t n_spans, int32_t* d_labels,
                                         double* d_scores, void* stream) {
-    if (!m) return fail(LDGPU_EINVAL, "model is NULL");
-    if (n_docs < 0) return fail(LDGPU_EINVAL, "n_docs < 0");
-    if (n_spans < 0) return fail(LDGPU_EINVAL, "n_spans < 0");
-    if (int rc = check_span_args(width, stride)) return rc;
-    if (n_spans > 0 && (!d_offsets || !d_span_offsets || !d_labels || (n_bytes > 0 && !d_bytes)))
-        return fail(LDGPU_EINVAL, "device pointer is NULL");
-    if (((uintptr_t)d_bytes & 3) != 0) return fail(LDGPU_EINVAL, "d_bytes must be 4-byte aligned");
+    const bool null_ptr = n_spans > 0 && (!d_offsets || !d_span_offsets || !d_labels || (n_bytes > 0 && !d_bytes));
+    if (int rc = device_call_begin(m, n_docs, d_bytes, null_ptr, [&] {
+            if (n_spans < 0) return fail(LDGPU_EINVAL, "n_spans < 0");
+            return check_span_args(width, stride);
+        }))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipSetDevice(m->ctx->device));
     const int64_t chunk = span_chunk_spans(width);
     for (int64_t g0 = 0; g0 < n_spans; g0 += chunk) {
         SpanParams sp{};
@@ -2310,158 +2366,60 @@ extern "C" int ldgpu_score_spans_device(ldgpu_model* m, const uint8_t* d_bytes, 
         if (int rc = span_chunk(m, sp, d_labels + g0, d_scores ? d_scores + g0 * m->L : nullptr, m->d_err, st))
             return rc;
     }
-    if (m->has_bad && n_spans > 0) {
+    if (n_spans > 0) {
         if (int rc = check_row_error(m, m->d_err, st)) return rc;
     }
     return ok();
 }
 
-namespace {
-int score_spans_host(ldgpu_model* m, ScorePipe* pp, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs,
-                     const std::vector<int64_t>& soff, int32_t width, int32_t stride, int32_t* out_labels,
-                     double* out_scores) {
-    // score_host's two-stage pipeline over chunks of spans.  Per chunk the host
-    // copies in the source byte range its spans touch -- from the first span's
-    // first byte to the last span's end: the documents' bytes once, never the
-    // width / stride expansion -- with the chunk's view of the offsets: the
-    // documents' offsets relative to that range (the first document's may be
-    // negative: the chunk starts at one of its later spans) and their span
-    // offsets relative to the chunk's first span.
-    // (With scores the stage's score buffer bounds a chunk too, as in the top-k form.)
+// The span form of the host pipeline (run_score_pipe): chunks are fixed runs of
+// spans.  Per chunk the host copies in the source byte range its spans touch --
+// from the first span's first byte to the last span's end: the documents'
+// bytes once, never the width / stride expansion -- with the chunk's view of
+// the offsets: the documents' offsets relative to that range (the first
+// document's may be negative: the chunk starts at one of its later spans) and
+// their span offsets relative to the chunk's first span.
+extern "C" int ldgpu_score_spans(ldgpu_model* m, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs,
+                                 int32_t width, int32_t stride, int32_t* out_labels, double* out_scores) {
+    // (no document-length limit: only spans are scored, and width is below it)
+    if (int rc = check_host_call(m, bytes, offsets, n_docs, out_labels, "out_labels", false,
+                                 [&] { return check_span_args(width, stride); }))
+        return rc;
+    if (n_docs == 0) return ok();
+    std::vector<int64_t> soff((size_t)n_docs + 1);
+    host_span_offsets(offsets, n_docs, width, stride, soff.data());
+    const int64_t n_spans = soff[n_docs];
+    const ScoreCall call{bytes, offsets, n_docs, soff.data(), n_spans,
+                         {{&ScoreStage::labels, &ScoreStage::h_labels, out_labels, sizeof(int32_t)},
+                          {&ScoreStage::scores, &ScoreStage::h_scores, out_scores, sizeof(double) * m->L}}};
+    // (with scores the stage's score buffer bounds a chunk too, as in the top-k form)
     int64_t chunk = span_chunk_spans(width);
     if (out_scores) chunk = std::min(chunk, topk_chunk_docs(m->L));
-    const int64_t n_spans = soff[n_docs];
-    const bool pinned_in = nb_total_pinned(bytes, offsets, n_docs);
-    const bool pinned_out = is_pinned(out_labels) && (!out_scores || is_pinned(out_scores));
-    auto retire = [&](ScoreStage& st) -> int {
-        if (!st.busy) return LDGPU_OK;
-        HIP_TRY(hipEventSynchronize(st.done));
-        st.busy = false;
-        if (!pinned_out) {
-            memcpy(out_labels + st.d0, st.h_labels.p, sizeof(int32_t) * st.nd);
-            if (out_scores) par_memcpy(out_scores + st.d0 * m->L, st.h_scores.p, sizeof(double) * st.nd * m->L);
-        }
-        return LDGPU_OK;
-    };
     // the last document d with soff[d] <= g
     auto doc_of = [&](int64_t g) -> int64_t {
         return (int64_t)(std::upper_bound(soff.begin(), soff.begin() + n_docs, g) - soff.begin()) - 1;
     };
-    auto issue = [&](ScoreStage& st, int64_t g0, int64_t g1) -> int {
-        const int64_t nc = g1 - g0, dA = doc_of(g0), dB = doc_of(g1 - 1), ndc = dB - dA + 1;
+    auto cut = [&](int64_t g0) {
+        const int64_t g1 = std::min(n_spans, g0 + chunk), dA = doc_of(g0), dB = doc_of(g1 - 1);
         const int64_t lo = offsets[dA] + (g0 - soff[dA]) * stride;
         const int64_t hi = offsets[dB] + std::min<int64_t>((g1 - 1 - soff[dB]) * stride + width,
                                                            offsets[dB + 1] - offsets[dB]);
-        const int64_t nb = hi - lo;
-        HIP_TRY(st.bytes.ensure((size_t)nb + 16));
-        HIP_TRY(st.offsets.ensure(2 * sizeof(int64_t) * (ndc + 1)));
-        HIP_TRY(st.labels.ensure(sizeof(int32_t) * nc));
-        if (out_scores) HIP_TRY(st.scores.ensure(sizeof(double) * nc * m->L));
-        HIP_TRY(st.h_offsets.ensure(2 * sizeof(int64_t) * (ndc + 1)));
-        int64_t* ho = (int64_t*)st.h_offsets.p;
-        int64_t* hs = ho + ndc + 1;
-        for (int64_t i = 0; i <= ndc; ++i) {
-            ho[i] = offsets[dA + i] - lo;
-            hs[i] = soff[dA + i] - g0;
-        }
-        const uint8_t* src = bytes + lo;
-        if (nb && !pinned_in) {
-            HIP_TRY(st.h_bytes.ensure((size_t)nb));
-            par_memcpy(st.h_bytes.p, src, (size_t)nb);
-            src = (const uint8_t*)st.h_bytes.p;
-        }
-        if (nb) HIP_TRY(hipMemcpyAsync(st.bytes.p, src, nb, hipMemcpyHostToDevice, st.stream));
-        HIP_TRY(hipMemcpyAsync(st.offsets.p, ho, 2 * sizeof(int64_t) * (ndc + 1), hipMemcpyHostToDevice, st.stream));
+        return PipeChunk{g0, g1, lo, hi, dA, dB - dA + 1};
+    };
+    auto launch = [&](ScoreStage& st, const PipeChunk& ch, int32_t* d_err) -> int {
         SpanParams sp{};
         sp.bytes = (const uint8_t*)st.bytes.p;
-        sp.n_bytes = nb;
+        sp.n_bytes = ch.hi - ch.lo;
         sp.offsets = (const int64_t*)st.offsets.p;
-        sp.n_docs = ndc;
-        sp.span_offsets = sp.offsets + ndc + 1;
+        sp.n_docs = ch.n_docs;
+        sp.span_offsets = sp.offsets + ch.n_docs + 1;
         sp.width = width;
         sp.stride = stride;
         sp.g0 = 0;
-        sp.nc = nc;
-        if (int r = span_chunk(m, sp, (int32_t*)st.labels.p, out_scores ? (double*)st.scores.p : nullptr, pp->d_err,
-                               st.stream))
-            return r;
-        int32_t* lab_dst = out_labels + g0;
-        double* sc_dst = out_scores ? out_scores + g0 * m->L : nullptr;
-        if (!pinned_out) {
-            HIP_TRY(st.h_labels.ensure(sizeof(int32_t) * nc));
-            lab_dst = (int32_t*)st.h_labels.p;
-            if (out_scores) {
-                HIP_TRY(st.h_scores.ensure(sizeof(double) * nc * m->L));
-                sc_dst = (double*)st.h_scores.p;
-            }
-        }
-        HIP_TRY(hipMemcpyAsync(lab_dst, st.labels.p, sizeof(int32_t) * nc, hipMemcpyDeviceToHost, st.stream));
-        if (out_scores)
-            HIP_TRY(hipMemcpyAsync(sc_dst, st.scores.p, sizeof(double) * nc * m->L, hipMemcpyDeviceToHost,
-                                   st.stream));
-        HIP_TRY(hipEventRecord(st.done, st.stream));
-        st.d0 = g0;
-        st.nd = nc;
-        st.busy = true;
-        return LDGPU_OK;
+        sp.nc = ch.i1 - ch.i0;
+        return span_chunk(m, sp, (int32_t*)st.labels.p, out_scores ? (double*)st.scores.p : nullptr, d_err, st.stream);
     };
-    int k = 0;
-    int rc = LDGPU_OK;
-    for (int64_t g0 = 0; g0 < n_spans; g0 += chunk, ++k) {
-        ScoreStage& st = pp->stage[k & 1];
-        if ((rc = retire(st))) break;
-        if ((rc = issue(st, g0, std::min(n_spans, g0 + chunk)))) break;
-    }
-    // drain as score_host does: every queued copy completes before the call
-    // returns, also after an error
-    for (auto& st : pp->stage) {
-        const hipError_t e = hipStreamSynchronize(st.stream);
-        if (!rc && e != hipSuccess) rc = fail(LDGPU_EDEVICE, "score pipeline: %s", hipGetErrorString(e));
-    }
-    for (int i = 0; i < 2; ++i) {
-        ScoreStage& st = pp->stage[(k + i) & 1];
-        if (rc) {
-            st.busy = false;  // the call failed: its outputs are undefined
-            continue;
-        }
-        rc = retire(st);
-    }
-    if (rc) {
-        (void)hipMemset(pp->d_err, 0, sizeof(int32_t));  // no stale row error for the pipeline's next call
-        return rc;
-    }
-    if (m->has_bad) {
-        if (int r = check_row_error(m, pp->d_err, pp->stage[0].stream)) return r;
-    }
-    return LDGPU_OK;
-}
-}  // namespace
-
-// Thread-safe and concurrent like ldgpu_score: a pipeline of the context's pool.
-extern "C" int ldgpu_score_spans(ldgpu_model* m, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs,
-                                 int32_t width, int32_t stride, int32_t* out_labels, double* out_scores) {
-    if (!m) return fail(LDGPU_EINVAL, "model is NULL");
-    if (int rc = check_offsets(offsets, n_docs)) return rc;
-    if (int rc = check_span_args(width, stride)) return rc;
-    if (n_docs == 0) return ok();
-    if (!out_labels) return fail(LDGPU_EINVAL, "out_labels is NULL");
-    if (!bytes && offsets[n_docs] > offsets[0]) return fail(LDGPU_EINVAL, "bytes is NULL");
-    // (no document-length limit: only spans are scored, and width is below it)
-    std::vector<int64_t> soff((size_t)n_docs + 1);
-    int64_t g = 0;
-    for (int64_t d = 0; d < n_docs; ++d) {
-        soff[d] = g;
-        g += span_count(offsets[d + 1] - offsets[d], width, stride);
-    }
-    soff[n_docs] = g;
-    ldgpu_ctx* c = m->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    ScorePipe* pp = pipe_acquire(c);
-    if (!pp) return LDGPU_EDEVICE;
-    const int rc = score_spans_host(m, pp, bytes, offsets, n_docs, soff, width, stride, out_labels, out_scores);
-    pipe_release(c, pp);
-    if (rc) return rc;
-    return ok();
+    return with_pipe(m, [&](ScorePipe* pp) { return run_score_pipe(m, pp, call, cut, launch); });
 }
 
 // ---------------------------------------------------------------------- FIT
@@ -4326,8 +4284,7 @@ extern "C" int ldgpu_count(ldgpu_counts* c, const uint8_t* bytes, const int64_t*
     std::vector<int64_t> off;
     int64_t d0 = 0;
     while (d0 < n_docs) {
-        int64_t d1 = d0 + 1;
-        while (d1 < n_docs && d1 - d0 < kChunkDocs && offsets[d1 + 1] - offsets[d0] <= kChunkBytes) ++d1;
+        const int64_t d1 = chunk_end(offsets, n_docs, d0, kChunkDocs, kChunkBytes);
         const int64_t nd = d1 - d0, b0 = offsets[d0], nb = offsets[d1] - b0;
         off.resize(nd + 1);
         for (int64_t i = 0; i <= nd; ++i) off[i] = offsets[d0 + i] - b0;

@@ -13,7 +13,8 @@ import ldoracle as O
 import ldoracle_c as OC
 from conftest import GOLDEN
 from languagedetection import LanguageDetectorModel, _lib, encoding, synth
-from languagedetection.runtime import DeviceModel
+from languagedetection.runtime import DeviceModel, PinnedArray
+from test_gpu_topk import chunked_corpus
 
 pytestmark = pytest.mark.gpu
 
@@ -690,6 +691,79 @@ def test_failed_call_leaves_pipeline_clean(monkeypatch):
     assert np.array_equal(lab, ol) and np.array_equal(bits(sc), bits(os_))
     lab_full, _ = m.score(data, off)
     assert np.array_equal(lab_full[:300_000], ol)
+
+
+@pytest.mark.parametrize("chunk", [1, 7, 64])
+def test_score_chunk_docs_switch(chunk, monkeypatch):
+    """LDGPU_SCORE_CHUNK_DOCS (diagnostics library) cuts the labels form into
+    chunks of a few documents: the top-k tests' 100 documents (empty ones first
+    and last of a chunk of 7, lengths 1, 2, 64 and 65) equal the product
+    library's single chunk and the C oracle, labels and score bits."""
+    table, L, grams, data, off, os_ = chunked_corpus()
+    ol = oracle_c(table, L, grams, data, off, scores=False)[0]
+    ref_l, ref_s = DeviceModel(table, L, grams).score(data, off, want_scores=True)
+    assert np.array_equal(ref_l, ol) and np.array_equal(bits(ref_s), bits(os_))
+    monkeypatch.setenv("LDGPU_SCORE_CHUNK_DOCS", str(chunk))
+    diag = DeviceModel(table, L, grams, variant="diag")
+    lab, sc = diag.score(data, off, want_scores=True)
+    assert np.array_equal(lab, ref_l) and np.array_equal(bits(sc), bits(ref_s))
+    assert np.array_equal(diag.score(data, off)[0], ol)
+
+
+@pytest.mark.parametrize("want_scores", [False, True])
+def test_failed_chunked_call_leaves_pipeline_clean(want_scores, monkeypatch):
+    """Chunks of 7 documents, a failure injected at chunk 2 (diagnostics
+    library): chunks 0 and 1 are in flight when the call fails.  It drains, and
+    the next call on the pooled pipeline gives the oracle's labels and score
+    bits -- into pageable arrays, and (after another failed call) into pinned
+    arrays pre-filled with -1."""
+    table, L, grams, data, off, os_ = chunked_corpus()
+    ol = oracle_c(table, L, grams, data, off, scores=False)[0]
+    n = len(off) - 1
+    assert data.dtype == np.uint8 and off.dtype == np.int64   # (passed to the C ABI as they are)
+    m = DeviceModel(table, L, grams, variant="diag")
+    monkeypatch.setenv("LDGPU_SCORE_CHUNK_DOCS", "7")
+    pl, ps = PinnedArray(n, np.int32), PinnedArray((n, L), np.float64)
+    for pinned in (False, True):
+        monkeypatch.setenv("LDGPU_FAIL_CHUNK", "2")
+        with pytest.raises(_lib.LdgpuError, match="injected failure"):
+            m.score(data, off, want_scores=want_scores)
+        monkeypatch.delenv("LDGPU_FAIL_CHUNK")
+        if pinned:
+            pl.array[:] = -1
+            ps.array[:] = -1.0
+            lab, sc = pl.array, ps.array if want_scores else None
+            m._check(m.lib.ldgpu_score(m.h, data.ctypes.data, off.ctypes.data, n, lab.ctypes.data,
+                                       sc.ctypes.data if want_scores else None))
+        else:
+            lab, sc = m.score(data, off, want_scores=want_scores)
+        assert np.array_equal(lab, ol), pinned
+        assert (sc is None) == (not want_scores)
+        if want_scores:
+            assert np.array_equal(bits(sc), bits(os_)), pinned
+    pl.close()
+    ps.close()
+
+
+def test_failed_call_resets_the_error_word(monkeypatch):
+    """A model with a wrong-length row, chunks of 7 documents.  The documents
+    of chunks 0 and 1 hit the row, then the call fails by injection at chunk 2:
+    it reports the injected failure and clears the pipeline's error word, so
+    the next call (no hit of the row) succeeds instead of raising the stale
+    row error, and a call that does hit the row still raises it."""
+    m = DeviceModel({b"ab": [1.0], b"xy": [0.0, 1.0]}, 2, [2], variant="diag")
+    monkeypatch.setenv("LDGPU_SCORE_CHUNK_DOCS", "7")
+    docs = [b"xyxy", b"zz"] * 15
+    bad = list(docs)
+    bad[3] = bad[9] = b"zzabzz"   # in chunks 0 and 1
+    monkeypatch.setenv("LDGPU_FAIL_CHUNK", "2")
+    with pytest.raises(_lib.LdgpuError, match="injected failure"):
+        m.score(*encoding.pack(bad))
+    monkeypatch.delenv("LDGPU_FAIL_CHUNK")
+    assert m.score(*encoding.pack(docs))[0].tolist() == [1, 0] * 15
+    with pytest.raises(ValueError, match="BLAS.axpy size mismatch"):
+        m.score(*encoding.pack(bad))
+    assert m.score(*encoding.pack(docs))[0].tolist() == [1, 0] * 15
 
 
 def test_config5_shape_parity_large_profile_global_filter():

@@ -229,6 +229,37 @@ def test_chunks_cut_inside_documents(chunk, monkeypatch):
         monkeypatch.delenv("LDGPU_SPAN_CHUNK_SPANS")
 
 
+@pytest.mark.parametrize("want_scores", [False, True])
+def test_failed_call_leaves_pipeline_clean(want_scores, monkeypatch):
+    """The host call in chunks of 5 spans, a failure injected at chunk 2
+    (diagnostics library): chunks 0 and 1 are in flight when the call fails.
+    It drains, and the next call on the pooled pipeline gives the oracle's
+    labels and score bits -- into pageable arrays, and (after another failed
+    call) into pinned arrays pre-filled with -1."""
+    kind, width, stride = "ordered", 64, 32
+    L, grams = KINDS[kind][0], KINDS[kind][1]
+    data, off = chunk_corpus(81, 40)
+    ol, os_, _, _ = oracle(kind_table(kind), L, grams, data, off, width, stride)
+    n = len(ol)
+    assert n >= 4 * 5
+    m = kind_model(kind, "diag")
+    monkeypatch.setenv("LDGPU_SPAN_CHUNK_SPANS", "5")
+    pl, ps = PinnedArray(n, np.int32), PinnedArray((n, L), np.float64)
+    for out in ({}, {"out_labels": pl.array, "out_scores": ps.array if want_scores else None}):
+        monkeypatch.setenv("LDGPU_FAIL_CHUNK", "2")
+        with pytest.raises(_lib.LdgpuError, match="injected failure"):
+            m.score_spans(data, off, width, stride, want_scores=want_scores)
+        monkeypatch.delenv("LDGPU_FAIL_CHUNK")
+        pl.array[:] = -1
+        ps.array[:] = -1.0
+        got = m.score_spans(data, off, width, stride, want_scores=want_scores, **out)
+        assert (got[1] is None) == (not want_scores)
+        assert not out or (got[0] is pl.array and (got[1] is ps.array or not want_scores))
+        assert_spans(got, ol, os_, "pinned" if out else "pageable")
+    pl.close()
+    ps.close()
+
+
 def test_host_pipeline_pinned_pageable_and_threads(monkeypatch):
     monkeypatch.setenv("LDGPU_SPAN_CHUNK_SPANS", "64")
     kind, width, stride = "ordered", 64, 32

@@ -1,6 +1,7 @@
 """SCORE's top-k output (ldgpu_score_topk / ldgpu_score_topk_device) against
 languagedetection.topk.rank applied to the C oracle's scores: labels exact,
 scores bit for bit, entry 0 equal to the label SCORE gives."""
+import functools
 import json
 import math
 import os
@@ -11,7 +12,7 @@ import pytest
 
 import ldoracle_c as OC
 from conftest import GOLDEN
-from languagedetection import LanguageDetectorModel, encoding, topk
+from languagedetection import LanguageDetectorModel, _lib, encoding, topk
 from languagedetection.runtime import DeviceModel, PinnedArray
 
 pytestmark = pytest.mark.gpu
@@ -224,11 +225,11 @@ def test_nan_inf_signed_zero_rows(L, at):
 
 
 # --------------------------------------------------------------- chunking
-def test_chunked_device_call(monkeypatch):
-    """The diagnostics library with chunks of 7 documents: 100 documents, some
-    empty, some first / last of a chunk, on torch tensors and a non-default
-    stream, equal the unchunked product result and the oracle."""
-    monkeypatch.setenv("LDGPU_TOPK_CHUNK_DOCS", "7")
+@functools.lru_cache(maxsize=None)
+def chunked_corpus():
+    """(table, L, grams, data, off, the oracle's scores): 100 documents for
+    chunks of 7 -- empty ones first and last of a chunk (0, 6, 7, 13, 14, 98,
+    99), and lengths 1, 2, 64 and 65 around a chunk boundary."""
     rng = np.random.default_rng(41)
     L, grams = 20, [1, 2, 3]
     table = make_table(rng, L, 300, grams, "mask")
@@ -237,6 +238,17 @@ def test_chunked_device_call(monkeypatch):
     lens[[20, 21, 27, 28]] = [1, 2, 64, 65]
     data, off = encoding.pack([bytes(rng.choice(ALPHABET, size=int(x))) for x in lens])
     scores = oracle_scores(table, L, grams, data, off)
+    for a in (data, scores):  # (off stays writable: torch.from_numpy takes it as it is)
+        a.setflags(write=False)
+    return table, L, grams, data, off, scores
+
+
+def test_chunked_device_call(monkeypatch):
+    """The diagnostics library with chunks of 7 documents: 100 documents, some
+    empty, some first / last of a chunk, on torch tensors and a non-default
+    stream, equal the unchunked product result and the oracle."""
+    monkeypatch.setenv("LDGPU_TOPK_CHUNK_DOCS", "7")
+    table, L, grams, data, off, scores = chunked_corpus()
     diag = DeviceModel(table, L, grams, variant="diag")
     prod = DeviceModel(table, L, grams)
     for k in (1, 3, 16):
@@ -255,6 +267,53 @@ def test_chunked_device_call(monkeypatch):
     assert_topk(device_topk(diag, data, off[one], 3), scores[20:21], 3)
     tl, ts = diag.score_topk(data[:0], off[:1], 3)
     assert tl.shape == (0, 3)
+
+
+@pytest.mark.parametrize("want_scores", [False, True])
+def test_failed_call_leaves_pipeline_clean(want_scores, monkeypatch):
+    """The host call in chunks of 7 documents, a failure injected at chunk 2
+    (diagnostics library): chunks 0 and 1 are in flight when the call fails.
+    It drains, and the next call on the pooled pipeline gives the oracle's top
+    3 -- into pageable arrays, and (after another failed call) into pinned
+    arrays pre-filled with -1."""
+    table, L, grams, data, off, scores = chunked_corpus()
+    n, k = len(off) - 1, 3
+    m = DeviceModel(table, L, grams, variant="diag")
+    monkeypatch.setenv("LDGPU_TOPK_CHUNK_DOCS", "7")
+    pl, ps = PinnedArray((n, k), np.int32), PinnedArray((n, k), np.float64)
+    for out in ({}, {"out_labels": pl.array, "out_scores": ps.array if want_scores else None}):
+        monkeypatch.setenv("LDGPU_FAIL_CHUNK", "2")
+        with pytest.raises(_lib.LdgpuError, match="injected failure"):
+            m.score_topk(data, off, k, want_scores=want_scores)
+        monkeypatch.delenv("LDGPU_FAIL_CHUNK")
+        pl.array[:] = -1
+        ps.array[:] = -1.0
+        got = m.score_topk(data, off, k, want_scores=want_scores, **out)
+        assert (got[1] is None) == (not want_scores)
+        assert not out or (got[0] is pl.array and (got[1] is ps.array or not want_scores))
+        assert_topk(got, scores, k)
+    pl.close()
+    ps.close()
+
+
+def test_failed_call_resets_the_error_word(monkeypatch):
+    """A model with a wrong-length row, chunks of 7 documents: documents of
+    chunks 0 and 1 hit the row, then the call fails by injection at chunk 2.
+    The message is the injected one, and the pipeline's error word is cleared:
+    the next call (no hit of the row) succeeds, one that hits it still raises."""
+    m = DeviceModel({b"ab": [1.0], b"xy": [0.0, 1.0]}, 2, [2], variant="diag")
+    monkeypatch.setenv("LDGPU_TOPK_CHUNK_DOCS", "7")
+    docs = [b"xyxy", b"zz"] * 15
+    bad = list(docs)
+    bad[3] = bad[9] = b"zzabzz"   # in chunks 0 and 1
+    monkeypatch.setenv("LDGPU_FAIL_CHUNK", "2")
+    with pytest.raises(_lib.LdgpuError, match="injected failure"):
+        m.score_topk(*encoding.pack(bad), 2)
+    monkeypatch.delenv("LDGPU_FAIL_CHUNK")
+    assert m.score_topk(*encoding.pack(docs), 2)[0].tolist() == [[1, 0], [0, 1]] * 15
+    with pytest.raises(ValueError, match="BLAS.axpy size mismatch"):
+        m.score_topk(*encoding.pack(bad), 2)
+    assert m.score_topk(*encoding.pack(docs), 2)[0].tolist() == [[1, 0], [0, 1]] * 15
 
 
 # ---------------------------------------------------------- host pipeline
