@@ -21,7 +21,10 @@
 //              candidates to a per-wave LDS queue with mbcnt, so the queue is
 //              in reference order: n outer, position inner.  Count and class
 //              mode need no order: on their split-verify path one wave scan
-//              queues a document's candidates of lengths 3..7 (scan_append).
+//              queues a document's candidates of lengths 3..7 (scan_append),
+//              and a staged fast-path document gives each lane four
+//              CONSECUTIVE positions instead: one 11-byte run read once, every
+//              hash and key derived from it (lane runs, probe_count_runs).
 //   verify    64 queued keys at a time probe the global table (2-choice
 //              cuckoo slots, 5-slot buckets for big count-mode tables, a
 //              two-word table for keys of 8..15 bytes).
@@ -1231,7 +1234,203 @@ __device__ __forceinline__ bool scan_append(const ScoreParams& p, const WaveLds&
     return true;
 }
 
-template <bool FULL, int S, bool STAGED, int KEYED, bool WIDE, int MODE = 3>
+// Lane runs (LDGPU_LANE_RUNS): on the scanned split path of a staged fast-path
+// document, lane i owns the four CONSECUTIVE window positions 4 i .. 4 i + 3
+// instead of i, i + 64, i + 128, i + 192.  The 4 x 8 bytes those windows span
+// are the 11 bytes of one run, so the lane reads the aligned dwords from
+// (base >> 2) + i (three when base & 3 == 0, a fourth otherwise), realigns them
+// once by the wave-uniform base & 3 into bytes 0..11 of its run, and derives
+// the 3-byte groups at run offsets 0..6 once, each with a constant-shift
+// v_alignbit (offsets 0 and 4 are the run registers themselves).  With g[o] the
+// group at offset o (its top byte is whatever follows: mul24 / mulhi24 and
+// v_bfe ignore it), position k of the lane takes
+//   its prefix-Bloom word from g[k], the filter bit of length N from
+//   g[k + min(N - 3, 3)], its 1- and 2-byte direct keys from g[k].
+// Queue entries are N << kPosBits | 4 lane + k; verify_issue / flush rebuild the
+// keys from LDS by position as before.
+// Bound: lane 63 reads dwords (base >> 2) + 63 .. + 65, and + 66 only when
+// base & 3 != 0 -- exactly dword (base + 63) / 4 + 50, the furthest word
+// load_windows reads for the same document (the fourth read is clamped onto the
+// third when the base is aligned).
+// Every other path (no direct tables, keyed / wide / pack / ordered kernels,
+// the general path, documents read from global memory, and the per-length
+// fallback of a document with more than kQueueCap candidates) keeps Windows.
+#ifndef LDGPU_LANE_RUNS
+#define LDGPU_LANE_RUNS 1
+#endif
+template <int MODE, bool STAGED, int KEYED, bool WIDE>
+constexpr bool kLaneRuns = LDGPU_LANE_RUNS && LDGPU_SCAN_APPEND && LDGPU_SPLIT_VERIFY && LDGPU_BLOOM_BITS == 1 &&
+                           (MODE == 3 || MODE == 4) && STAGED && KEYED == 0 && !WIDE;
+
+// The tail cut of the lane-run layout, kept from one document to the next:
+// bit 8 k + (N - 3) of keep = the window of length N = 3..7 at position
+// 4 lane + k ends inside a document of `len` bytes (cm's layout: one v_and
+// cuts a document), bit 8 k + 5 / 8 k + 6 = the 1- / 2-byte window there does
+// (direct_count_runs).  Recomputed only when the length changes, a
+// wave-uniform compare: equal-length documents reuse it.
+struct RunCut {
+    uint32_t keep;
+    int32_t len;  // the length keep was built for (-1: none yet)
+};
+
+__device__ __forceinline__ void run_cut(RunCut& cut, int32_t len, int lane) {
+    if (__builtin_amdgcn_readfirstlane(cut.len) == len) return;
+    const int32_t left = len - 4 * lane;  // bytes from the lane's first position to the document's end
+    uint32_t keep = 0;
+#pragma unroll
+    for (int k = 0; k < kSub; ++k) {
+        const int32_t t = left - k;
+        const uint32_t b = ((1u << min(max(t - 2, 0), 5)) - 1u) | (t >= 1 ? 0x20u : 0u) | (t >= 2 ? 0x40u : 0u);
+        keep |= b << (8 * k);
+    }
+    cut.keep = keep;
+    cut.len = len;
+}
+
+// direct_count (non-pack) on the lane-run layout: the keys from the shared
+// groups g[0..3], the windows' validity from the cut (bit 8 k + 4 + N).  The
+// 2-byte lookup keeps its batch structure: all bases, then all languages.
+template <int N>
+__device__ __forceinline__ void direct_count_runs(const ScoreParams& p, const WaveLds& wl, const uint32_t* img,
+                                                  const uint32_t (&g)[7], uint32_t keep) {
+    const uint8_t* l1 = reinterpret_cast<const uint8_t*>(img + p.direct_off);
+    const uint16_t* b2 = reinterpret_cast<const uint16_t*>(img + p.direct_off + 64);
+    const uint8_t* l2 = reinterpret_cast<const uint8_t*>(img + p.direct_off + 64 + 1024);
+    uint32_t* cnt = count_area(wl);
+    const uint32_t inc = p.mult[N];
+    uint32_t lang[kSub];
+    bool hit[kSub];
+    if constexpr (N == 1) {
+#pragma unroll
+        for (int k = 0; k < kSub; ++k) lang[k] = l1[g[k] & 0xffu];
+#pragma unroll
+        for (int k = 0; k < kSub; ++k) hit[k] = lang[k] < 0xffu;
+    } else {
+        uint32_t w[kSub];
+#pragma unroll
+        for (int k = 0; k < kSub; ++k) w[k] = img[kBmp1Words + bmp2_word(g[k])];
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < kSub; ++k) {
+            hit[k] = __builtin_amdgcn_ubfe(w[k], g[k], 1) != 0u;
+            any |= hit[k];
+        }
+        if (!any) return;
+        // (a position that is no hit reads in range too: see direct_count)
+        uint32_t base[kSub];
+#pragma unroll
+        for (int k = 0; k < kSub; ++k) base[k] = b2[bmp2_word(g[k])];
+#pragma unroll
+        for (int k = 0; k < kSub; ++k)
+            lang[k] = l2[base[k] + __builtin_popcount(__builtin_amdgcn_ubfe(w[k], 0, g[k]))];
+#pragma unroll
+        for (int k = 0; k < kSub; ++k) asm volatile("" : "+v"(lang[k]));
+    }
+#pragma unroll
+    for (int k = 0; k < kSub; ++k)
+        if (hit[k] && ((keep >> (8 * k + 4 + N)) & 1u)) count_inc<false>(cnt, lang[k], inc);
+}
+
+// filter bits of length N for the lane's four consecutive positions
+template <int N>
+__device__ __forceinline__ void run_bits(const uint32_t (&w3)[kSub], const uint32_t (&g)[7], uint32_t fm,
+                                         uint32_t& cm) {
+    if (!((fm >> N) & 1u)) return;
+    constexpr int o = N < 6 ? N - 3 : 3;  // pf_shift(N) / 8
+#pragma unroll
+    for (int k = 0; k < kSub; ++k) {
+        const uint32_t t = __builtin_amdgcn_ubfe(w3[k], mulhi24(g[k + o], pf_mult(N)), 1);
+        cm = k == 0 ? lshl_or<N - 3>(t, cm)
+                    : (k == 1 ? lshl_or<8 + N - 3>(t, cm) : (k == 2 ? lshl_or<16 + N - 3>(t, cm) : lshl_or<24 + N - 3>(t, cm)));
+    }
+}
+
+// probe_count_all's scanned split path on the lane-run layout (fm has
+// kFmDirect set; a staged fast-path document).  Returns false, with nothing
+// queued or counted, when the document has more than kQueueCap candidates: the
+// caller then reloads it in the Windows layout and takes the per-length path.
+template <int S, int MODE>
+__device__ __forceinline__ bool probe_count_runs(const ScoreParams& p, const WaveLds& wl, const uint32_t* img,
+                                                 const uint32_t* bloom, int32_t len, int lane, const DocSrc& src,
+                                                 uint32_t fm, RunCut& cut) {
+    uint32_t g[7];
+    {
+        const uint32_t sh = (uint32_t)src.base & 3u;  // wave-uniform
+        const uint32_t* w = src.lds + ((uint32_t)src.base >> 2) + lane;
+        // the fourth dword only for an unaligned base (the bound above)
+        const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[sh ? 3 : 2];
+        const uint32_t r0 = __builtin_amdgcn_alignbyte(w1, w0, sh);  // run bytes 0..3
+        const uint32_t r1 = __builtin_amdgcn_alignbyte(w2, w1, sh);  // 4..7
+        const uint32_t r2 = __builtin_amdgcn_alignbyte(w3, w2, sh);  // 8..11
+        g[0] = r0;
+        g[1] = __builtin_amdgcn_alignbit(r1, r0, 8);
+        g[2] = __builtin_amdgcn_alignbit(r1, r0, 16);
+        g[3] = __builtin_amdgcn_alignbit(r1, r0, 24);
+        g[4] = r1;
+        g[5] = __builtin_amdgcn_alignbit(r2, r1, 8);
+        g[6] = __builtin_amdgcn_alignbit(r2, r1, 16);
+    }
+    uint32_t w3[kSub];
+#pragma unroll
+    for (int k = 0; k < kSub; ++k) w3[k] = bloom[pf_word(g[k], p.bloom_shift)];
+    run_cut(cut, len, lane);
+    uint32_t cm = 0;
+    if (!ablated(p, 16)) {
+        run_bits<3>(w3, g, fm, cm);
+        run_bits<4>(w3, g, fm, cm);
+        run_bits<5>(w3, g, fm, cm);
+        run_bits<6>(w3, g, fm, cm);
+        run_bits<7>(w3, g, fm, cm);
+    }
+    cm &= cut.keep;  // (cm's bits 5..7 of every byte are clear)
+    const uint32_t c = (uint32_t)__builtin_popcount(cm);
+    const uint32_t sum = wave_scan_u32(c);
+    const uint32_t total = rdlane(sum, 63);
+    if (total > (uint32_t)kQueueCap) return false;
+#ifdef LDGPU_STATS
+    if (p.stats) {  // documents scanned, store-loop iterations (the largest c of a lane)
+        const uint32_t it = wave_max_u32(c);
+        if (lane == 0) {
+            atomicAdd(&p.stats[2], 1ull);
+            atomicAdd(&p.stats[3], (unsigned long long)it);
+        }
+    }
+#endif
+    if (total) {
+        // (opaque lane: see append_sb)
+        uint32_t l = (uint32_t)lane;
+        asm volatile("" : "+v"(l));
+        const uint32_t tag = 4u * l + (3u << kPosBits);
+        uint32_t at = (uint32_t)(uintptr_t)wl.queue + 4u * (sum - c);  // LDS offset of the lane's first entry
+        while (cm) {
+            // bit j = 8 k + (N - 3): the entry N << kPosBits | 4 lane + k
+            const uint32_t j = (uint32_t)__builtin_ctz(cm);
+            *(lds_u32*)(size_t)at = ((j & 7u) << kPosBits) + ((j >> 3) + tag);
+            at += 4u;
+            cm &= cm - 1u;
+        }
+    }
+    const int qn = (int)total;
+    VerifyIssue v;
+    const bool pending = qn > 0 && !ablated(p, 1);
+    if (pending) verify_issue<true>(p, wl, qn, src, lane, v);
+    if (!ablated(p, 8)) {
+        if ((fm >> 1) & 1u) direct_count_runs<1>(p, wl, img, g, cut.keep);
+        if ((fm >> 2) & 1u) direct_count_runs<2>(p, wl, img, g, cut.keep);
+    }
+    if (pending) {
+        verify_complete<S, MODE>(p, wl, v);
+        if (qn > 64) {
+            double acc[S];  // unused in count mode
+            flush<S, MODE, true, 0, false, false>(p, wl, qn, src, acc, lane, true, 64);
+        }
+    }
+    return true;
+}
+
+// SCAN: try scan_append (false for the callers that have lane runs, which
+// reach this function only where the scan does not apply or has overflowed)
+template <bool FULL, int S, bool STAGED, int KEYED, bool WIDE, int MODE = 3, bool SCAN = true>
 __device__ __forceinline__ void probe_count_all(const ScoreParams& p, const WaveLds& wl, const uint32_t* img,
                                                 const FWords& f, const Windows& x, int32_t len, int lane, int& qn,
                                                 const DocSrc& src) {
@@ -1264,7 +1463,7 @@ __device__ __forceinline__ void probe_count_all(const ScoreParams& p, const Wave
     // prefix Bloom; the per-length path otherwise, and for a document with
     // more candidates than the queue holds
     bool scanned = false;
-    if constexpr (LDGPU_SCAN_APPEND && KEYED == 0 && !WIDE && LDGPU_BLOOM_BITS == 1) {
+    if constexpr (SCAN && LDGPU_SCAN_APPEND && KEYED == 0 && !WIDE && LDGPU_BLOOM_BITS == 1) {
         if (split) scanned = scan_append<FULL>(p, wl, f, x, len, lane, qn, fm);
     }
     if (!scanned) {
@@ -1544,13 +1743,24 @@ __device__ __forceinline__ void score_pack(const ScoreParams& p, const WaveLds& 
 template <int S, int MODE, bool STAGED, int KEYED, bool WIDE>
 __device__ __forceinline__ int score_doc(const ScoreParams& p, const WaveLds& wl, const uint32_t* img,
                                           const uint32_t* bloom, int64_t doc, int64_t b, int64_t len,
-                                          const DocSrc& src, int lane) {
+                                          const DocSrc& src, int lane, RunCut& cut) {
     double acc[S];
 #pragma unroll
     for (int s = 0; s < S; ++s) acc[s] = 0.0;
     int qn = 0;
     bool general = !(len >= p.maxg && len <= 64 * kSub);
-    if (!general) {
+    // lane runs: the layout is decided before any window is loaded (the
+    // eligibility is wave-uniform: direct tables present = the split path)
+    bool runs_done = false;
+    if constexpr (kLaneRuns<MODE, STAGED, KEYED, WIDE>) {
+        if (!general && p.n_fast && !ablated(p, 2)) {
+            uint32_t fm = __builtin_amdgcn_readfirstlane(p.fast_mask | (p.direct_words ? 1u << kFmDirect : 0u));
+            asm volatile("" : "+s"(fm));
+            if ((fm >> kFmDirect) & 1u)
+                runs_done = probe_count_runs<S, MODE>(p, wl, img, bloom, (int32_t)len, lane, src, fm, cut);
+        }
+    }
+    if (!general && !runs_done) {
         // fast path: every window is full-length (klen = n) and one
         // superblock covers the document, so every gram length reuses the
         // same window bytes and prefix-Bloom words.  Count mode (hit order
@@ -1564,10 +1774,13 @@ __device__ __forceinline__ int score_doc(const ScoreParams& p, const WaveLds& wl
             FWords f;
             load_fwords<KEYED>(p, bloom, x, f);
             if constexpr (MODE == 3 || MODE == 4) {
+                constexpr bool SCAN = !kLaneRuns<MODE, STAGED, KEYED, WIDE>;
                 if (len >= 192 + p.maxg)
-                    probe_count_all<true, S, STAGED, KEYED, WIDE, MODE>(p, wl, img, f, x, (int32_t)len, lane, qn, src);
+                    probe_count_all<true, S, STAGED, KEYED, WIDE, MODE, SCAN>(p, wl, img, f, x, (int32_t)len, lane, qn,
+                                                                              src);
                 else
-                    probe_count_all<false, S, STAGED, KEYED, WIDE, MODE>(p, wl, img, f, x, (int32_t)len, lane, qn, src);
+                    probe_count_all<false, S, STAGED, KEYED, WIDE, MODE, SCAN>(p, wl, img, f, x, (int32_t)len, lane, qn,
+                                                                               src);
             }
             uint64_t gq = p.gpack[0];
             for (int gi = 0; gi < (MODE == 3 || MODE == 4 ? 0 : p.n_fast); ++gi) {
@@ -1776,12 +1989,15 @@ __global__ __launch_bounds__(kScoreWaves * 64, kScoreMinWgPerCu * kScoreWaves / 
         __builtin_amdgcn_wave_barrier();
     }
 
+    RunCut cut{0u, -1};  // lane runs: the tail cut of the last document length (score_doc)
+
     if constexpr (IND) {
         const int64_t nw = (int64_t)gridDim.x * kScoreWaves;
         for (int64_t i = (int64_t)blockIdx.x * kScoreWaves + wave; i < n_ind; i += nw) {
             const int64_t d = p.doc_idx[i];
             const int64_t b = p.offsets[d], len = p.offsets[d + 1] - b;
-            const int lab = score_doc<S, MODE, false, BL, WIDE>(p, wl, lds, bloom, d, b, len, DocSrc{nullptr, b}, lane);
+            const int lab =
+                score_doc<S, MODE, false, BL, WIDE>(p, wl, lds, bloom, d, b, len, DocSrc{nullptr, b}, lane, cut);
             if (lane == 0) p.labels[d] = lab;
         }
         return;
@@ -1867,7 +2083,7 @@ __global__ __launch_bounds__(kScoreWaves * 64, kScoreMinWgPerCu * kScoreWaves / 
                         }
                     }
                 }
-                const int lab = score_doc<S, MODE, true, BL, WIDE>(p, wl, lds, bloom, g0 + i, b, len, src, lane);
+                const int lab = score_doc<S, MODE, true, BL, WIDE>(p, wl, lds, bloom, g0 + i, b, len, src, lane, cut);
                 if (lane == 0) wl.labels[i] = lab;
                 ++i;
             }
@@ -1876,7 +2092,7 @@ __global__ __launch_bounds__(kScoreWaves * 64, kScoreMinWgPerCu * kScoreWaves / 
                 const int64_t b = rdlane_i64(offv, i);
                 const int64_t len = rdlane_i64(offv, i + 1) - b;
                 const DocSrc src{nullptr, b};
-                const int lab = score_doc<S, MODE, false, BL, WIDE>(p, wl, lds, bloom, g0 + i, b, len, src, lane);
+                const int lab = score_doc<S, MODE, false, BL, WIDE>(p, wl, lds, bloom, g0 + i, b, len, src, lane, cut);
                 if (lane == 0) wl.labels[i] = lab;
             }
         }
