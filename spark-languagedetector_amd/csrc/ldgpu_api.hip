@@ -3794,9 +3794,19 @@ int count_launch_v3(ldgpu_counts* c, const uint8_t* d_bytes, int64_t n_bytes, co
         // balanced by records, about 4 workgroups per CU in all (2 resident:
         // the tail of the launch stays short); a
         // workgroup's record region holds its records, its block directory
-        // records / threshold + 2 blocks
+        // records / threshold + 2 blocks.  Every language present has a
+        // workgroup of its own, so the count is not bounded by the CUs: a
+        // language takes ceil(lwin / target) <= lwin / target + 1 parts, all
+        // of them <= share + present, and part2 holds a prefix over a group's
+        // workgroups in LDS (kMaxEmitWg, ldgpu_fit.h).  The share for
+        // splitting is what the present languages and the padding leave of
+        // that bound: 4 per CU on any device of up to 1022 CUs.
         const int64_t Wk = std::accumulate(lwin.begin(), lwin.end(), (int64_t)0);
-        const int64_t target = std::max<int64_t>(1, (Wk + 4 * x->cus - 1) / (4 * x->cus));
+        int64_t present = 0;
+        for (int l = 0; l < L; ++l) present += lwin[l] > 0;
+        static_assert(kMaxEmitWg % kSplits == 0 && kMaxEmitWg - kSplits > LDGPU_MAX_LANGS, "emit workgroup bound");
+        const int64_t share = std::min<int64_t>(4 * (int64_t)x->cus, kMaxEmitWg - kSplits - present);
+        const int64_t target = std::max<int64_t>(1, (Wk + share - 1) / share);
         wg_doc.clear();
         wg_rec.clear();
         wg_dir.clear();
@@ -3884,6 +3894,8 @@ int count_launch_v3(ldgpu_counts* c, const uint8_t* d_bytes, int64_t n_bytes, co
         if (trace) tt[0] = now_ms();
         const int64_t d0 = cur.d0, d1 = cur.d1, acc = cur.acc, dirs = cur.dirs;
         const int grid_a = cur.grid_a;
+        if (grid_a > kMaxEmitWg)  // (the plan's share keeps to it: nothing is launched past part2's prefix array)
+            return fail(LDGPU_EDEVICE, "fit plan: %d emit workgroups, at most %d", grid_a, kMaxEmitWg);
         const std::vector<int64_t>& meta = cur.meta;
         const std::vector<int32_t>& wg_lang = cur.wg_lang;
         const std::vector<int32_t>& plen = cur.plen;

@@ -92,6 +92,12 @@ constexpr int kBlkWords = 6144;                 // u64 words of records per emit
 constexpr int kHdr = 68;                        // u32 per block header (kQ + 1 used)
 constexpr int kEmitWaves = 16;
 constexpr int kSplits = 8;                      // emit workgroup groups (part2 inputs)
+// Most emit workgroups of a batch (grid_a).  Every language with a document in
+// the batch has at least one, so the bound is the 4096 languages of a table
+// plus a share of as many for splitting the heavy ones; the host plan
+// (count_launch_v3) keeps to it, and part2 holds the block prefix of one
+// group's kMaxEmitWg / kSplits workgroups in LDS.
+constexpr int kMaxEmitWg = 8192;
 constexpr uint64_t kCntBits = 52;               // K >= 2: count bits of the last record word
 // emit rounds: a wave step adds at most 64 x sub records (sub = 4 positions per
 // lane for K = 1, 1 otherwise); a block is flushed once it could not take

@@ -1904,7 +1904,7 @@ struct Part2Lds {
     uint32_t lstart[kQ];
     uint64_t cur[kQ];      // records written per q2 sub-bucket so far
     int64_t base[kQ];      // global index of the round's first record of q2, minus its LDS start
-    int32_t gpre[257];     // blocks of the group's emit workgroups (exclusive prefix)
+    int32_t gpre[kMaxEmitWg / kSplits + 1];  // blocks of the group's emit workgroups (exclusive prefix)
     int64_t unit, uoff;    // next run and the records of it already taken
 };
 
@@ -2913,7 +2913,12 @@ hipError_t launch_fit_offsets(const PartParams& p, hipStream_t stream) {
     return hipGetLastError();
 }
 
+// two workgroups of part2 on a CU's 160 KiB of LDS, the group prefix included
+static_assert(2 * sizeof(Part2Lds<1>) <= 160 * 1024, "part2 LDS");
+
 hipError_t launch_part2(int K, const PartParams& p, hipStream_t stream) {
+    // gpre holds grid_a / kSplits + 1 prefixes
+    if (p.grid_a < kSplits || p.grid_a % kSplits || p.grid_a > kMaxEmitWg) return hipErrorInvalidValue;
     const dim3 g(kQ * kSplits), b(kEmitWaves * 64);
     if (K == 1) hipLaunchKernelGGL(part2_kernel<1>, g, b, 0, stream, p);
     else if (K == 2) hipLaunchKernelGGL(part2_kernel<2>, g, b, 0, stream, p);

@@ -331,7 +331,9 @@ def test_count_paths_match_oracle(L, grams, variant, env, monkeypatch):
 def test_count_4096_languages(variant, monkeypatch):
     """The largest language count: two-word records (12 language bits leave
     a one-word record no count bits at grams up to 6), a few short documents
-    per language id spread over all 4096 (dense export rows stay small)."""
+    per language id spread over all 4096 (dense export rows stay small).
+    At most 40 languages are present here; test_gpu_fit_many_langs.py has
+    every one of 4096 present, in this shape and in the other record forms."""
     if variant == "diag":
         monkeypatch.setenv("LDGPU_FIT_BATCH_WINDOWS", "3000")
         monkeypatch.setenv("LDGPU_FIT_SORT_BATCH", "300")
