@@ -134,6 +134,10 @@ int ldgpu_model_info(const ldgpu_model* model, int32_t* mode, int64_t* n_keys,
                                                   finite values: per-(value, language) hit counts and a
                                                   rounding bound; documents the bound cannot separate
                                                   replayed in reference order */
+#define LDGPU_LAYOUT_NARROW_SLOTS       0x800  /* order-free scoring (count / class mode, LDS Bloom): the keys
+                                                  of 3 and 4 bytes verified from a second table of 8-byte
+                                                  slots (no key of 5 bytes or more, one language per such
+                                                  row) */
 int ldgpu_model_layout(const ldgpu_model* model, int32_t* flags);
 /* The model's language count (a caller sizing score buffers, e.g. the JNI
  * shim, takes it from the model rather than trusting its own). */

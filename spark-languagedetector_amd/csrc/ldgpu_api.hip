@@ -620,6 +620,8 @@ struct ldgpu_model {
     Slot* d_slots = nullptr;
     WideSlot* d_wslots = nullptr;  // wide keys (8..15 bytes), nullptr: none
     uint64_t wslot_cap = 0;
+    NarrowSlot* d_nslots = nullptr;  // order-free modes: the keys of 3 and 4 bytes in 8-byte slots, nullptr: none
+    uint64_t nslot_cap = 0;
     Bucket* d_buckets = nullptr;  // count mode key table
     uint64_t n_buckets = 0;
     uint32_t* d_filter = nullptr;
@@ -674,7 +676,7 @@ void model_free(ldgpu_model* m) {
                             "store-loop iterations %llu\n", st[0], st[1], st[2], st[3]);
         (void)hipFree(m->d_stats);
     }
-    for (void* p : {(void*)m->d_slots, (void*)m->d_wslots, (void*)m->d_buckets, (void*)m->d_filter, (void*)m->d_masks, (void*)m->d_vals, (void*)m->d_rows,
+    for (void* p : {(void*)m->d_slots, (void*)m->d_wslots, (void*)m->d_nslots, (void*)m->d_buckets, (void*)m->d_filter, (void*)m->d_masks, (void*)m->d_vals, (void*)m->d_rows,
                     (void*)m->d_fold, (void*)m->d_err, (void*)m->d_gslots, (void*)m->d_arena, (void*)m->d_koff,
                     (void*)m->d_lbits})
         if (p) (void)hipFree(p);
@@ -1431,6 +1433,80 @@ int model_build(ldgpu_ctx* ctx, int32_t n_langs, const int32_t* gram_lengths, in
         }
     }
 
+    // narrow slots (NarrowSlot, ldgpu_common.h): the order-free LDS-Bloom
+    // kernels (count mode, class mode) verify the keys of >= 3 bytes from a
+    // second cuckoo table of 8-byte slots when every such key has at most 4
+    // bytes, names exactly one language and is no wrong-length row -- the shape
+    // of a fitted top-K table, whose per-language best grams are the short ones
+    // unique to a language.  Same load and walk-then-double policy as `slots`,
+    // which stays: the ordered modes, 1-/2-byte queue entries and every table
+    // outside the rule read it.  Diagnostics: LDGPU_NO_NARROW_SLOTS=1 keeps the
+    // full slots.
+    std::vector<NarrowSlot> nslots;
+    {
+        bool narrow = (m->mode == 3 || m->n_cls > 0) && !keyed && nw == 0 && !use_buckets && !dense;
+        if (const char* s = diag_env("LDGPU_NO_NARROW_SLOTS")) narrow &= atoi(s) == 0;
+        uint32_t mult[kNarrowMaxLen + 1] = {};
+        for (int i = 0; i < n_grams; ++i)
+            if (gram_lengths[i] >= 3 && gram_lengths[i] <= kNarrowMaxLen) ++mult[gram_lengths[i]];
+        std::vector<NarrowSlot> nkeys;  // the slots to place
+        for (int64_t i = 0; i < nn && narrow; ++i) {
+            const int len = key_len(keys[i]);
+            if (len < 3) continue;
+            int bits = 0;
+            uint32_t lang = 0;
+            for (int s = 0; s < S; ++s) {
+                const uint64_t w = masks[(size_t)i * S + s];
+                if (w && !bits) lang = 64u * (uint32_t)s + (uint32_t)__builtin_ctzll(w);
+                bits += __builtin_popcountll(w);
+            }
+            const uint32_t cidx = lang_slot(i, lang);
+            if (len > kNarrowMaxLen || bits != 1 || t.bad[i] || cidx >= (1u << kNarrowMultShift)) {
+                narrow = false;
+                break;
+            }
+            nkeys.push_back(NarrowSlot{(uint32_t)keys[i],
+                                       cidx | mult[len] << kNarrowMultShift | (uint32_t)len << kNarrowLenShift});
+        }
+        for (m->nslot_cap = next_pow2(std::max<uint64_t>(16, (uint64_t)(2.5 * (double)nkeys.size()) + 1));
+             narrow && !nkeys.empty(); m->nslot_cap *= 2) {
+            const int slog = log2u(m->nslot_cap);
+            if (slog > 28) {  // (placement keeps failing: the full slots serve)
+                narrow = false;
+                break;
+            }
+            auto npos = [&](const NarrowSlot& s, int which) {
+                uint32_t h1, h2;
+                narrow_hash(s.key, s.meta >> kNarrowLenShift, h1, h2);
+                return (uint64_t)((which ? h2 : h1) >> (32 - slog));
+            };
+            nslots.assign(m->nslot_cap, NarrowSlot{0u, 0u});  // (meta 0: length 0, an empty slot)
+            bool ok_all = true;
+            for (size_t i = 0; i < nkeys.size() && ok_all; ++i) {
+                NarrowSlot cur = nkeys[i];
+                uint64_t at = npos(cur, 0);
+                if (nslots[at].meta != 0u && nslots[npos(cur, 1)].meta == 0u) at = npos(cur, 1);
+                bool placed = false;
+                for (int step = 0; step < 2000; ++step) {
+                    if (nslots[at].meta == 0u) {
+                        nslots[at] = cur;
+                        placed = true;
+                        break;
+                    }
+                    std::swap(cur, nslots[at]);
+                    const uint64_t a = npos(cur, 0), b = npos(cur, 1);
+                    at = at == a ? b : a;
+                }
+                ok_all = placed;
+            }
+            if (ok_all) break;
+        }
+        if (!narrow || nkeys.empty()) {
+            nslots.clear();
+            m->nslot_cap = 0;
+        }
+    }
+
     // filter image: exact bitmaps of the 1- and 2-byte keys, then the prefix
     // Bloom filter of the longer ones (ldgpu_common.h).  The bloom is staged
     // in LDS up to 64 KiB, else read from global memory (L2 / Infinity Cache).
@@ -1571,6 +1647,7 @@ int model_build(ldgpu_ctx* ctx, int32_t n_langs, const int32_t* gram_lengths, in
     hipError_t e = hipSetDevice(ctx->device);
     if (e == hipSuccess) e = upload(&m->d_slots, slots, &m->device_bytes);
     if (e == hipSuccess && nw > 0) e = upload(&m->d_wslots, wslots, &m->device_bytes);
+    if (e == hipSuccess && !nslots.empty()) e = upload(&m->d_nslots, nslots, &m->device_bytes);
     if (e == hipSuccess && use_buckets) e = upload(&m->d_buckets, buckets, &m->device_bytes);
     if (e == hipSuccess) e = upload(&m->d_filter, filter, &m->device_bytes);
     if (e == hipSuccess) e = upload(&m->d_masks, masks, &m->device_bytes);
@@ -1659,6 +1736,7 @@ extern "C" int ldgpu_model_layout(const ldgpu_model* m, int32_t* flags) {
     if (b->kb_lines) f |= LDGPU_LAYOUT_KEYED_BLOOM_LINES;
     if (b->d_buckets) f |= LDGPU_LAYOUT_BUCKETS;
     if (b->d_wslots) f |= LDGPU_LAYOUT_WIDE_KEYS;
+    if (b->d_nslots) f |= LDGPU_LAYOUT_NARROW_SLOTS;
     if (b->direct_words) f |= LDGPU_LAYOUT_DIRECT;
     if (b->pack_ok) f |= LDGPU_LAYOUT_PACKS;
     if (b->n_cls && m->blocks.empty()) f |= LDGPU_LAYOUT_CLASSES;
@@ -1722,6 +1800,7 @@ int class_replay(ldgpu_model* m, const ScoreParams& p4, hipStream_t st) {
         p1.n_cls = 0;
         p1.hit_words = 0;
         p1.direct_words = 0;
+        p1.nslots = nullptr;
         gram_lists(m, p1, 1);
         e = launch_score(p1, m->slices, 1, m->lds_filter, score_grid(m, n), st);
     }
@@ -1879,6 +1958,10 @@ int score_launch(ldgpu_model* m, const uint8_t* d_bytes, int64_t n_bytes, const 
     }
     gram_lists(m, p, mode);
     if (mode != 3 && mode != 4) p.direct_words = 0;  // the ordered replay reads no direct tables
+    if ((mode == 3 || mode == 4) && m->d_nslots) {   // ... and no narrow slots
+        p.nslots = m->d_nslots;
+        p.nslot_shift32 = (uint32_t)(32 - log2u(m->nslot_cap));
+    }
     // count mode, labels only: a fast-path document (<= 256 B, so far below
     // count_argmax_len) takes the count argmax (score kernel kFmArgmax)
     if (mode == 3 && p.count_argmax_len >= 256 && !d_scores && !d_best) p.fast_mask |= 1u << 17;

@@ -184,6 +184,31 @@ __host__ __device__ __forceinline__ void slot_hash(uint32_t lo, uint32_t hi, uin
     h2 = mul24(b ^ (c << 8), 0x27D4EBu) ^ mul24(a, 0x165667u) ^ mul24(c ^ (b >> 12), 0xD3A265u);
 }
 
+// Narrow slot table (NarrowSlot below): the 2-choice cuckoo table of a table's
+// keys of 3 and 4 bytes, in 8-byte slots.  key = the bytes little-endian, zero
+// above klen.  Two 24-bit multiplies per slot position: bytes 0..2, and bytes
+// 1..3 with the length XORed into byte 1 -- "abc" and "abc\0" hash apart --
+// summed, so the second is one v_mad_u32_u24;
+// slot 1 = h1 >> (32 - log2 cap), slot 2 = h2 >> (32 - log2 cap).
+__host__ __device__ __forceinline__ void narrow_hash(uint32_t key, uint32_t klen, uint32_t& h1, uint32_t& h2) {
+    const uint32_t b = (key >> 8) ^ klen;
+    h1 = mul24(key, 0x9E3779u) + mul24(b, 0x85EBCAu);
+    h2 = mul24(key, 0x165667u) + mul24(b, 0x27D4EBu);
+}
+
+// Slot of the narrow table (8 B, one dwordx2 load): the key's bytes and
+//   meta = counter index | multiplicity << kNarrowMultShift | klen << kNarrowLenShift
+// (counter index: what Slot::pad holds, the row's one language or class mode's
+// counter; multiplicity: of klen in gramLengths).  An empty slot has length 0,
+// which no window has: it equals no key, the all-zero windows included.
+struct alignas(8) NarrowSlot {
+    uint32_t key;
+    uint32_t meta;
+};
+constexpr uint32_t kNarrowMultShift = 16;
+constexpr uint32_t kNarrowLenShift = 29;
+constexpr int kNarrowMaxLen = 4;
+
 // Cuckoo slot positions of the wide-key table: the two words folded into
 // slot_hash's input
 __host__ __device__ __forceinline__ void wide_hash(uint64_t lo, uint64_t hi, uint32_t& h1, uint32_t& h2) {

@@ -88,6 +88,11 @@ struct ScoreParams {
     // the device wrote: no readback), its label stored to labels[doc_idx[i]]
     const int64_t* doc_idx;     // nullptr: document i is document i
     const unsigned long long* n_docs_dev;
+    // order-free modes (3, 4), LDS-Bloom kernels: the narrow slot table of the
+    // keys of >= 3 bytes (NarrowSlot, ldgpu_common.h), which the verify then
+    // reads instead of `slots`; nullptr: the table has none
+    const NarrowSlot* nslots;
+    uint32_t nslot_shift32;     // narrow slot = h1 (h2) >> nslot_shift32 of narrow_hash
 };
 
 // languages per block of a blocked model (L > kBlockLangs)

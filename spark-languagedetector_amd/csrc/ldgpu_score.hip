@@ -323,6 +323,107 @@ struct VerifyIssue {
     bool valid;
 };
 
+// Narrow slots (LDGPU_NARROW_SLOTS): a table whose keys of >= 3 bytes all have
+// at most 4, one language each and no wrong-length row (the host's rule,
+// model_build) carries them a second time in 8-byte slots -- key bytes | counter
+// index, multiplicity, length (NarrowSlot, ldgpu_common.h) -- and the order-free
+// LDS-Bloom kernels verify against those: a 32-bit key from two staged dwords,
+// two 24-bit multiplies per slot position, one 8-byte load per slot, a compare
+// of key and length, counter and increment from the slot that matched.  No
+// p.mult load, no wrong-length ballot and no mask walk: the rule excludes those
+// rows.  A queue entry of a 1- or 2-byte key (tables without direct tables, the
+// general path) keeps the full slots.  Selected by one wave-uniform test of
+// p.nslots, read through the cold pointer at the verify (no SGPR held across
+// the document loop); the keyed, wide and ordered kernels compile without it.
+#ifndef LDGPU_NARROW_SLOTS
+#define LDGPU_NARROW_SLOTS 1
+#endif
+template <int MODE, int KEYED, bool WIDE>
+constexpr bool kNarrowSlots = LDGPU_NARROW_SLOTS && (MODE == 3 || MODE == 4) && KEYED == 0 && !WIDE;
+
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+// the narrow table of a launch (nullptr: none) and its slot shift
+struct NarrowTab {
+    const NarrowSlot* slots;
+    uint32_t shift;
+};
+template <int MODE, int KEYED, bool WIDE>
+__device__ __forceinline__ NarrowTab narrow_tab(const ScoreParams& p) {
+    if constexpr (kNarrowSlots<MODE, KEYED, WIDE>)
+        return with_cold<KEYED>(p, [](const auto& q) { return NarrowTab{q.nslots, q.nslot_shift32}; });
+    else
+        return NarrowTab{nullptr, 0u};
+}
+
+// the 32-bit key of a window of klen = 3 or 4 bytes (zero above klen) and the
+// loads of its two narrow slots
+template <bool STAGED>
+__device__ __forceinline__ void narrow_issue(const ScoreParams& p, const NarrowTab& nt, const DocSrc& src, uint32_t e,
+                                             bool pack, uint32_t& key, uint32_t& tag, u32x2& a, u32x2& c) {
+    const uint32_t klen = e >> kPosBits;
+    const int64_t at = src.base + (int64_t)(e & (pack ? 255u : (1u << kPosBits) - 1u));
+    const uint32_t sh = (uint32_t)(at & 3);
+    uint32_t w0, w1;
+    if constexpr (STAGED) {
+        const uint32_t i = (uint32_t)(at >> 2);
+        w0 = src.lds[i];
+        w1 = src.lds[i + 1];
+    } else {
+        const uint32_t* W = reinterpret_cast<const uint32_t*>(p.bytes);
+        w0 = ld_dw(W, at >> 2, p.last_dword);
+        w1 = ld_dw(W, (at >> 2) + 1, p.last_dword);
+    }
+    const uint32_t win = __builtin_amdgcn_alignbyte(w1, w0, sh);
+    key = klen == 3u ? win & 0xffffffu : win;
+    tag = klen << kNarrowLenShift;
+    uint32_t h1, h2;
+    narrow_hash(key, klen, h1, h2);
+    const u32x2* sl = reinterpret_cast<const u32x2*>(nt.slots);
+    a = sl[h1 >> nt.shift];
+    c = sl[h2 >> nt.shift];
+}
+
+// the meta word of the slot that holds (key, length), 0 = neither does (a
+// key's meta has its length, >= 3, in the top bits)
+__device__ __forceinline__ uint32_t narrow_match(uint32_t key, uint32_t tag, const u32x2& a, const u32x2& c) {
+    const bool ha = a.x == key && (a.y & (7u << kNarrowLenShift)) == tag;
+    const bool hc = c.x == key && (c.y & (7u << kNarrowLenShift)) == tag;
+    return ha ? a.y : (hc ? c.y : 0u);
+}
+
+// The split verify on the narrow table (the split path queues keys of >= 3
+// bytes only, so every entry is narrow).  The fields are set in the lanes below
+// qn alone, and read there alone: no lane pays for a default.
+struct NarrowIssue {
+    u32x2 a, c;     // the key's two narrow slots
+    uint32_t key;   // its bytes
+    uint32_t tag;   // its length << kNarrowLenShift
+};
+
+template <bool STAGED>
+__device__ __forceinline__ void narrow_verify_issue(const ScoreParams& p, const NarrowTab& nt, const WaveLds& w, int qn,
+                                                    const DocSrc& src, int lane, NarrowIssue& v) {
+    __builtin_amdgcn_wave_barrier();
+    if (lane < qn) narrow_issue<STAGED>(p, nt, src, w.queue[lane], false, v.key, v.tag, v.a, v.c);
+}
+
+__device__ __forceinline__ void narrow_verify_complete(const ScoreParams& p, const WaveLds& w, int qn, int lane,
+                                                       const NarrowIssue& v) {
+    uint32_t meta = 0u;
+    if (lane < qn) meta = narrow_match(v.key, v.tag, v.a, v.c);
+#ifdef LDGPU_STATS
+    if (p.stats) {
+        const int ng = __popcll(__ballot(meta != 0u));
+        if ((threadIdx.x & 63) == 0) {
+            atomicAdd(&p.stats[0], (unsigned long long)min(qn, 64));
+            atomicAdd(&p.stats[1], (unsigned long long)ng);
+        }
+    }
+#endif
+    if (meta) count_inc<false>(count_area(w), meta & 0xffffu, __builtin_amdgcn_ubfe(meta, kNarrowMultShift, 8));
+}
+
 template <bool STAGED>
 __device__ __forceinline__ void verify_issue(const ScoreParams& p, const WaveLds& w, int qn, const DocSrc& src,
                                              int lane, VerifyIssue& v) {
@@ -404,6 +505,7 @@ template <int S, int MODE, bool STAGED, int KEYED, bool PACK = false, bool WIDE 
 __device__ __forceinline__ void flush(const ScoreParams& p, const WaveLds& w, int qn, const DocSrc& src,
                                       double (&acc)[S], int lane, bool weighted = false, int q_begin = 0) {
     __builtin_amdgcn_wave_barrier();
+    const NarrowTab nt = narrow_tab<MODE, KEYED, WIDE>(p);
     for (int q0 = q_begin; q0 < qn; q0 += 64) {
         const int j = q0 + lane;
         uint32_t row = 0xffffffffu;
@@ -415,11 +517,25 @@ __device__ __forceinline__ void flush(const ScoreParams& p, const WaveLds& w, in
         if (j < qn) {
             const uint32_t e = w.queue[j];
             const int klen = (int)(e >> kPosBits);
-            if ((MODE == 3 || MODE == 4) && weighted) inc = p.mult[klen];
+            // narrow slots: the table's keys of >= 3 bytes (a 1- or 2-byte entry reads the full slots)
+            const bool nar = kNarrowSlots<MODE, KEYED, WIDE> && nt.slots && klen >= 3;
+            if ((MODE == 3 || MODE == 4) && weighted && !nar) inc = p.mult[klen];
             if (PACK) coff = ((e >> 8) & (kPackDocs - 1u)) * 64u * S;
             const int64_t pos = (int64_t)(e & (PACK ? 255u : (1u << kPosBits) - 1u));
             if (WIDE && klen > kMaxGram) {  // (WIDE kernels: tables holding wide keys)
                 wide_lookup<STAGED, MODE, S>(p, src, pos, klen, row, lang1, v, m0);
+            } else if (nar) {
+                // both slots' loads before either compare (the register pin, as below)
+                uint32_t key, tag;
+                u32x2 a, c;
+                narrow_issue<STAGED>(p, nt, src, e, PACK, key, tag, a, c);
+                asm volatile("" : "+v"(a), "+v"(c));
+                const uint32_t meta = narrow_match(key, tag, a, c);
+                if (meta) {  // (one language, right length: the host's rule)
+                    row = 0;
+                    lang1 = meta & 0xffffu;
+                    if (weighted) inc = __builtin_amdgcn_ubfe(meta, kNarrowMultShift, 8);
+                }
             } else {
             uint32_t w0, w1, w2, sh;
             window_words<STAGED>(p, src, pos, w0, w1, w2, sh);
@@ -1411,19 +1527,28 @@ __device__ __forceinline__ bool probe_count_runs(const ScoreParams& p, const Wav
         }
     }
     const int qn = (int)total;
-    VerifyIssue v;
     const bool pending = qn > 0 && !ablated(p, 1);
-    if (pending) verify_issue<true>(p, wl, qn, src, lane, v);
-    if (!ablated(p, 8)) {
-        if ((fm >> 1) & 1u) direct_count_runs<1>(p, wl, img, g, cut.keep);
-        if ((fm >> 2) & 1u) direct_count_runs<2>(p, wl, img, g, cut.keep);
-    }
-    if (pending) {
-        verify_complete<S, MODE>(p, wl, v);
-        if (qn > 64) {
-            double acc[S];  // unused in count mode
-            flush<S, MODE, true, 0, false, false>(p, wl, qn, src, acc, lane, true, 64);
+    const auto direct = [&] {
+        if (!ablated(p, 8)) {
+            if ((fm >> 1) & 1u) direct_count_runs<1>(p, wl, img, g, cut.keep);
+            if ((fm >> 2) & 1u) direct_count_runs<2>(p, wl, img, g, cut.keep);
         }
+    };
+    const NarrowTab nt = narrow_tab<MODE, 0, false>(p);
+    if (kNarrowSlots<MODE, 0, false> && nt.slots) {
+        NarrowIssue v;
+        if (pending) narrow_verify_issue<true>(p, nt, wl, qn, src, lane, v);
+        direct();
+        if (pending) narrow_verify_complete(p, wl, qn, lane, v);
+    } else {
+        VerifyIssue v;
+        if (pending) verify_issue<true>(p, wl, qn, src, lane, v);
+        direct();
+        if (pending) verify_complete<S, MODE>(p, wl, v);
+    }
+    if (pending && qn > 64) {
+        double acc[S];  // unused in count mode
+        flush<S, MODE, true, 0, false, false>(p, wl, qn, src, acc, lane, true, 64);
     }
     return true;
 }
@@ -1491,6 +1616,11 @@ __device__ __forceinline__ void probe_count_all(const ScoreParams& p, const Wave
         append_sb(wl.queue, qn, m, n, 0, lane);
     }
     if (split) {
+        // (this split verify keeps the full slots, which hold every key: in the
+        // LDS-Bloom kernels it serves only documents read in place and the
+        // last candidates of one that overflowed the queue -- the others take
+        // the lane runs -- and a second copy of the direct counts here cost
+        // the S >= 2 kernels VGPR spills)
         VerifyIssue v;
         const bool pending = qn > 0 && !ablated(p, 1);
         if (pending) verify_issue<STAGED>(p, wl, qn, src, lane, v);
