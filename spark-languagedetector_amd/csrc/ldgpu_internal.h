@@ -112,6 +112,10 @@ constexpr int kScoreWaves = LDGPU_SCORE_WAVES;  // waves per workgroup (768 thre
 #endif
 constexpr int kScoreMinWgPerCu = LDGPU_SCORE_MIN_WG;
 constexpr int kQueueCap = 288;             // candidate entries (u32) per wave (>= 256 + slack)
+// run-format queue entries (the lane-run path of the order-free kernels,
+// ldgpu_score.hip): position << kRunLenBits | key length - kRunMinLen
+constexpr uint32_t kRunLenBits = 3;
+constexpr uint32_t kRunMinLen = 3;
 constexpr int kBufBytes = 1024;            // staged bytes of a document group per wave (one 64 x 16-B LDS-DMA)
 constexpr int kBufWords = kBufBytes / 4 + 4;
 constexpr int kMaxLdsBloomLog2 = 14;       // bloom words in LDS up to 64 KiB

@@ -42,6 +42,7 @@
 // one superblock); in count mode consecutive short ones share a superblock
 // (packs).  Shorter documents (partial windows) and longer ones loop n outer,
 // superblocks inner.
+#include <cstddef>
 #include <type_traits>
 
 //
@@ -356,11 +357,47 @@ __device__ __forceinline__ NarrowTab narrow_tab(const ScoreParams& p) {
         return NarrowTab{nullptr, 0u};
 }
 
+// Queue entry layouts.  Every producer but one stores klen << kPosBits |
+// position (append_sb, scan_append, append_pack, the general path).  The
+// lane-run store loop (probe_count_runs) stores the RUN format instead:
+//   e = (4 lane + k) << kRunLenBits | (N - kRunMinLen)
+// which is its bit index j = 8 k + (N - 3) plus the lane constant lane << 5 --
+// one add per entry -- and decodes for free: e >> 3 is the position, e & 7 the
+// length less 3, and (e << 29) + (3 << 29) the narrow length tag in one
+// v_lshl_add.  RUNQ (compile time) names the layout to the consumers of a
+// lane-run queue: narrow_verify_issue / narrow_issue, verify_issue and the
+// flush of the candidates past the first 64.
+template <bool RUNQ>
+__device__ __forceinline__ uint32_t entry_len(uint32_t e) {
+    return RUNQ ? (e & ((1u << kRunLenBits) - 1u)) + kRunMinLen : e >> kPosBits;
+}
+template <bool RUNQ>
+__device__ __forceinline__ uint32_t entry_pos(uint32_t e) {
+    return RUNQ ? e >> kRunLenBits : e & ((1u << kPosBits) - 1u);
+}
+static_assert(kNarrowLenShift + kRunLenBits == 32, "the run entry's length bits shift into the narrow tag");
+
 // the 32-bit key of a window of klen = 3 or 4 bytes (zero above klen) and the
 // loads of its two narrow slots
-template <bool STAGED>
+template <bool STAGED, bool RUNQ = false>
 __device__ __forceinline__ void narrow_issue(const ScoreParams& p, const NarrowTab& nt, const DocSrc& src, uint32_t e,
                                              bool pack, uint32_t& key, uint32_t& tag, u32x2& a, u32x2& c) {
+    if constexpr (RUNQ) {
+        // (a lane-run queue: a staged document, so base + position fits 32 bits)
+        static_assert(STAGED, "run-format entries come from staged documents");
+        tag = (e << kNarrowLenShift) + (kRunMinLen << kNarrowLenShift);
+        const uint32_t klen = tag >> kNarrowLenShift;
+        const uint32_t at = (uint32_t)src.base + entry_pos<true>(e);
+        const uint32_t w0 = src.lds[at >> 2], w1 = src.lds[(at >> 2) + 1];
+        const uint32_t win = __builtin_amdgcn_alignbyte(w1, w0, at & 3u);
+        key = klen == 3u ? win & 0xffffffu : win;
+        uint32_t h1, h2;
+        narrow_hash(key, klen, h1, h2);
+        const u32x2* sl = reinterpret_cast<const u32x2*>(nt.slots);
+        a = sl[h1 >> nt.shift];
+        c = sl[h2 >> nt.shift];
+        return;
+    }
     const uint32_t klen = e >> kPosBits;
     const int64_t at = src.base + (int64_t)(e & (pack ? 255u : (1u << kPosBits) - 1u));
     const uint32_t sh = (uint32_t)(at & 3);
@@ -401,11 +438,11 @@ struct NarrowIssue {
     uint32_t tag;   // its length << kNarrowLenShift
 };
 
-template <bool STAGED>
+template <bool STAGED, bool RUNQ = false>
 __device__ __forceinline__ void narrow_verify_issue(const ScoreParams& p, const NarrowTab& nt, const WaveLds& w, int qn,
                                                     const DocSrc& src, int lane, NarrowIssue& v) {
     __builtin_amdgcn_wave_barrier();
-    if (lane < qn) narrow_issue<STAGED>(p, nt, src, w.queue[lane], false, v.key, v.tag, v.a, v.c);
+    if (lane < qn) narrow_issue<STAGED, RUNQ>(p, nt, src, w.queue[lane], false, v.key, v.tag, v.a, v.c);
 }
 
 __device__ __forceinline__ void narrow_verify_complete(const ScoreParams& p, const WaveLds& w, int qn, int lane,
@@ -424,7 +461,7 @@ __device__ __forceinline__ void narrow_verify_complete(const ScoreParams& p, con
     if (meta) count_inc<false>(count_area(w), meta & 0xffffu, __builtin_amdgcn_ubfe(meta, kNarrowMultShift, 8));
 }
 
-template <bool STAGED>
+template <bool STAGED, bool RUNQ = false>
 __device__ __forceinline__ void verify_issue(const ScoreParams& p, const WaveLds& w, int qn, const DocSrc& src,
                                              int lane, VerifyIssue& v) {
     __builtin_amdgcn_wave_barrier();
@@ -434,10 +471,10 @@ __device__ __forceinline__ void verify_issue(const ScoreParams& p, const WaveLds
     v.a0 = v.c0 = u32x4{0u, 0u, 0u, 0u};
     if (v.valid) {
         const uint32_t e = w.queue[lane];
-        const int klen = (int)(e >> kPosBits);
+        const int klen = (int)entry_len<RUNQ>(e);
         v.inc = p.mult[klen];
         uint32_t w0, w1, w2, sh;
-        window_words<STAGED>(p, src, (int64_t)(e & ((1u << kPosBits) - 1u)), w0, w1, w2, sh);
+        window_words<STAGED>(p, src, (int64_t)entry_pos<RUNQ>(e), w0, w1, w2, sh);
         const uint64_t win = ((uint64_t)__builtin_amdgcn_alignbyte(w2, w1, sh) << 32) |
                              __builtin_amdgcn_alignbyte(w1, w0, sh);
         v.key = (win & (~0ull >> (64 - 8 * klen))) | ((uint64_t)klen << 56);
@@ -501,7 +538,8 @@ __device__ __forceinline__ void verify_complete(const ScoreParams& p, const Wave
 // PACK (MODE 3, packed short documents, score_pack): an entry's position is
 // its low 8 bits and bits 8..9 name the document of the pack, whose (u16)
 // counter block it counts into.
-template <int S, int MODE, bool STAGED, int KEYED, bool PACK = false, bool WIDE = false>
+// RUNQ: the queue holds run-format entries (the lane-run path's tail past 64).
+template <int S, int MODE, bool STAGED, int KEYED, bool PACK = false, bool WIDE = false, bool RUNQ = false>
 __device__ __forceinline__ void flush(const ScoreParams& p, const WaveLds& w, int qn, const DocSrc& src,
                                       double (&acc)[S], int lane, bool weighted = false, int q_begin = 0) {
     __builtin_amdgcn_wave_barrier();
@@ -516,19 +554,19 @@ __device__ __forceinline__ void flush(const ScoreParams& p, const WaveLds& w, in
         uint32_t coff = 0;  // PACK: the document's counter block
         if (j < qn) {
             const uint32_t e = w.queue[j];
-            const int klen = (int)(e >> kPosBits);
+            const int klen = (int)entry_len<RUNQ>(e);
             // narrow slots: the table's keys of >= 3 bytes (a 1- or 2-byte entry reads the full slots)
             const bool nar = kNarrowSlots<MODE, KEYED, WIDE> && nt.slots && klen >= 3;
             if ((MODE == 3 || MODE == 4) && weighted && !nar) inc = p.mult[klen];
             if (PACK) coff = ((e >> 8) & (kPackDocs - 1u)) * 64u * S;
-            const int64_t pos = (int64_t)(e & (PACK ? 255u : (1u << kPosBits) - 1u));
+            const int64_t pos = (int64_t)(RUNQ ? entry_pos<true>(e) : e & (PACK ? 255u : (1u << kPosBits) - 1u));
             if (WIDE && klen > kMaxGram) {  // (WIDE kernels: tables holding wide keys)
                 wide_lookup<STAGED, MODE, S>(p, src, pos, klen, row, lang1, v, m0);
             } else if (nar) {
                 // both slots' loads before either compare (the register pin, as below)
                 uint32_t key, tag;
                 u32x2 a, c;
-                narrow_issue<STAGED>(p, nt, src, e, PACK, key, tag, a, c);
+                narrow_issue<STAGED, RUNQ>(p, nt, src, e, PACK, key, tag, a, c);
                 asm volatile("" : "+v"(a), "+v"(c));
                 const uint32_t meta = narrow_match(key, tag, a, c);
                 if (meta) {  // (one language, right length: the host's rule)
@@ -1362,8 +1400,9 @@ __device__ __forceinline__ bool scan_append(const ScoreParams& p, const WaveLds&
 // v_bfe ignore it), position k of the lane takes
 //   its prefix-Bloom word from g[k], the filter bit of length N from
 //   g[k + min(N - 3, 3)], its 1- and 2-byte direct keys from g[k].
-// Queue entries are N << kPosBits | 4 lane + k; verify_issue / flush rebuild the
-// keys from LDS by position as before.
+// Queue entries are in the run format, (4 lane + k) << 3 | N - 3 (entry_pos /
+// entry_len); verify_issue / flush rebuild the keys from LDS by position as
+// before.
 // Bound: lane 63 reads dwords (base >> 2) + 63 .. + 65, and + 66 only when
 // base & 3 != 0 -- exactly dword (base + 63) / 4 + 50, the furthest word
 // load_windows reads for the same document (the fourth read is clamped onto the
@@ -1373,6 +1412,18 @@ __device__ __forceinline__ bool scan_append(const ScoreParams& p, const WaveLds&
 // fallback of a document with more than kQueueCap candidates) keeps Windows.
 #ifndef LDGPU_LANE_RUNS
 #define LDGPU_LANE_RUNS 1
+#endif
+// tuning switches of the lane-run path (build variants only): the 1-byte skip of
+// direct_count_runs, the staged loop's 32-bit document geometry, and the one
+// early load of the narrow table's pointer and shift
+#ifndef LDGPU_RUN_SKIP1
+#define LDGPU_RUN_SKIP1 1
+#endif
+#ifndef LDGPU_RUN_GEOM32
+#define LDGPU_RUN_GEOM32 1
+#endif
+#ifndef LDGPU_RUN_EARLY_COLD
+#define LDGPU_RUN_EARLY_COLD 1
 #endif
 template <int MODE, bool STAGED, int KEYED, bool WIDE>
 constexpr bool kLaneRuns = LDGPU_LANE_RUNS && LDGPU_SCAN_APPEND && LDGPU_SPLIT_VERIFY && LDGPU_BLOOM_BITS == 1 &&
@@ -1419,6 +1470,13 @@ __device__ __forceinline__ void direct_count_runs(const ScoreParams& p, const Wa
     if constexpr (N == 1) {
 #pragma unroll
         for (int k = 0; k < kSub; ++k) lang[k] = l1[g[k] & 0xffu];
+        // One wave-level branch around the four count regions: a table has few
+        // 1-byte keys, so most documents have no lane with a hit at any of its
+        // positions (0xff = no key; a hit past the document's end only keeps
+        // the wave on the count path, where the cut drops it).
+        if (LDGPU_RUN_SKIP1 &&
+            !__builtin_amdgcn_ballot_w64(min(min(lang[0], lang[1]), min(lang[2], lang[3])) < 0xffu))
+            return;
 #pragma unroll
         for (int k = 0; k < kSub; ++k) hit[k] = lang[k] < 0xffu;
     } else {
@@ -1461,6 +1519,52 @@ __device__ __forceinline__ void run_bits(const uint32_t (&w3)[kSub], const uint3
     }
 }
 
+// The store loop of the lane runs: the lane's n = popcount(cm) entries, lowest
+// bit of cm first, to consecutive queue words from `at`.  Bit j = 8 k + (N - 3)
+// of cm is the run-format entry (lane << 5) + j (entry_pos / entry_len).
+// kRunStoreUnroll entries per pass store through immediate offsets inside
+// nested regions -- exec only narrows, lane by finished lane, and is restored
+// once after the last -- and the back edge serves a lane with more (up to 20
+// with grams 3..7).  The regions test the count, not cm: the compare is off the
+// cm chain, and no lane's cm is re-materialised as 0 where it leaves.
+constexpr int kRunStoreUnroll = 4;
+template <int K = 0>
+__device__ __forceinline__ void run_store(lds_u32* at, uint32_t lane5, uint32_t& cm, uint32_t n) {
+    if constexpr (K < kRunStoreUnroll) {
+        if (n > (uint32_t)K) {
+            at[K] = lane5 + (uint32_t)__builtin_ctz(cm);
+            cm &= cm - 1u;
+            run_store<K + 1>(at, lane5, cm, n);
+        }
+    }
+}
+
+// nslots and nslot_shift32 of the launch as ONE 16-byte scalar load through the
+// cold pointer (they are neighbours in ScoreParams), for probe_count_runs to
+// issue before its Bloom reads: the wait then falls together with the Bloom
+// words', where two loads at their uses each drained the wave's LDS traffic.
+static_assert(offsetof(ScoreParams, nslots) % 16 == 0 &&
+                  offsetof(ScoreParams, nslot_shift32) == offsetof(ScoreParams, nslots) + 8 &&
+                  sizeof(ScoreParams) >= offsetof(ScoreParams, nslots) + 16,
+              "narrow_tab_early reads nslots | nslot_shift32 as one aligned 16-byte word");
+// (the pointer rebuilt from its bits names global memory, as a kernel argument
+// does: the slot loads stay global_load, not flat_load with its LDS-counter wait)
+__device__ __forceinline__ const NarrowSlot* global_slots(uint64_t bits) {
+    typedef const __attribute__((address_space(1))) NarrowSlot* GlobalSlots;
+    return (const NarrowSlot*)(GlobalSlots)(uintptr_t)bits;
+}
+template <int MODE>
+__device__ __forceinline__ NarrowTab narrow_tab_early(const ScoreParams& p) {
+    if constexpr (kNarrowSlots<MODE, 0, false> && LDGPU_COLD_PARAMS && LDGPU_RUN_EARLY_COLD) {
+        typedef const __attribute__((address_space(4))) char* ColdBytes;
+        typedef const __attribute__((address_space(4))) u32x4* ColdQuad;
+        const u32x4 q = *(ColdQuad)((ColdBytes)cold_params() + offsetof(ScoreParams, nslots));
+        return NarrowTab{global_slots(((uint64_t)q.y << 32) | q.x), q.z};
+    } else {
+        return narrow_tab<MODE, 0, false>(p);
+    }
+}
+
 // probe_count_all's scanned split path on the lane-run layout (fm has
 // kFmDirect set; a staged fast-path document).  Returns false, with nothing
 // queued or counted, when the document has more than kQueueCap candidates: the
@@ -1469,6 +1573,8 @@ template <int S, int MODE>
 __device__ __forceinline__ bool probe_count_runs(const ScoreParams& p, const WaveLds& wl, const uint32_t* img,
                                                  const uint32_t* bloom, int32_t len, int lane, const DocSrc& src,
                                                  uint32_t fm, RunCut& cut) {
+    NarrowTab nt{nullptr, 0u};
+    if constexpr (LDGPU_RUN_EARLY_COLD) nt = narrow_tab_early<MODE>(p);
     uint32_t g[7];
     {
         const uint32_t sh = (uint32_t)src.base & 3u;  // wave-uniform
@@ -1499,6 +1605,14 @@ __device__ __forceinline__ bool probe_count_runs(const ScoreParams& p, const Wav
         run_bits<7>(w3, g, fm, cm);
     }
     cm &= cut.keep;  // (cm's bits 5..7 of every byte are clear)
+    // the narrow table's pointer and shift are in SGPRs here, whole: the Bloom
+    // words have just been waited for, and no half of the pair sinks into the
+    // verify's exec region
+    if constexpr (LDGPU_RUN_EARLY_COLD) {
+        uint64_t ns = (uint64_t)(uintptr_t)nt.slots;
+        asm volatile("" : "+s"(ns), "+s"(nt.shift));
+        nt.slots = global_slots(ns);
+    }
     const uint32_t c = (uint32_t)__builtin_popcount(cm);
     const uint32_t sum = wave_scan_u32(c);
     const uint32_t total = rdlane(sum, 63);
@@ -1516,14 +1630,12 @@ __device__ __forceinline__ bool probe_count_runs(const ScoreParams& p, const Wav
         // (opaque lane: see append_sb)
         uint32_t l = (uint32_t)lane;
         asm volatile("" : "+v"(l));
-        const uint32_t tag = 4u * l + (3u << kPosBits);
-        uint32_t at = (uint32_t)(uintptr_t)wl.queue + 4u * (sum - c);  // LDS offset of the lane's first entry
-        while (cm) {
-            // bit j = 8 k + (N - 3): the entry N << kPosBits | 4 lane + k
-            const uint32_t j = (uint32_t)__builtin_ctz(cm);
-            *(lds_u32*)(size_t)at = ((j & 7u) << kPosBits) + ((j >> 3) + tag);
-            at += 4u;
-            cm &= cm - 1u;
+        const uint32_t lane5 = l << 5;
+        // the lane's first entry (LDS offset: the low half of the flat address)
+        lds_u32* at = (lds_u32*)(size_t)((uint32_t)(uintptr_t)wl.queue + 4u * (sum - c));
+        for (uint32_t n = c;; n -= kRunStoreUnroll, at += kRunStoreUnroll) {
+            run_store(at, lane5, cm, n);
+            if (n <= (uint32_t)kRunStoreUnroll) break;
         }
     }
     const int qn = (int)total;
@@ -1534,21 +1646,22 @@ __device__ __forceinline__ bool probe_count_runs(const ScoreParams& p, const Wav
             if ((fm >> 2) & 1u) direct_count_runs<2>(p, wl, img, g, cut.keep);
         }
     };
-    const NarrowTab nt = narrow_tab<MODE, 0, false>(p);
+    // (the queue holds run-format entries: every consumer below decodes RUNQ)
+    if constexpr (!LDGPU_RUN_EARLY_COLD) nt = narrow_tab<MODE, 0, false>(p);
     if (kNarrowSlots<MODE, 0, false> && nt.slots) {
         NarrowIssue v;
-        if (pending) narrow_verify_issue<true>(p, nt, wl, qn, src, lane, v);
+        if (pending) narrow_verify_issue<true, true>(p, nt, wl, qn, src, lane, v);
         direct();
         if (pending) narrow_verify_complete(p, wl, qn, lane, v);
     } else {
         VerifyIssue v;
-        if (pending) verify_issue<true>(p, wl, qn, src, lane, v);
+        if (pending) verify_issue<true, true>(p, wl, qn, src, lane, v);
         direct();
         if (pending) verify_complete<S, MODE>(p, wl, v);
     }
     if (pending && qn > 64) {
         double acc[S];  // unused in count mode
-        flush<S, MODE, true, 0, false, false>(p, wl, qn, src, acc, lane, true, 64);
+        flush<S, MODE, true, 0, false, false, true>(p, wl, qn, src, acc, lane, true, 64);
     }
     return true;
 }
@@ -1879,6 +1992,10 @@ __device__ __forceinline__ int score_doc(const ScoreParams& p, const WaveLds& wl
     for (int s = 0; s < S; ++s) acc[s] = 0.0;
     int qn = 0;
     bool general = !(len >= p.maxg && len <= 64 * kSub);
+    // (a staged document is at most kBufBytes long: the test on the low half,
+    // scalar 32-bit compares)
+    if constexpr (LDGPU_RUN_GEOM32 && kLaneRuns<MODE, STAGED, KEYED, WIDE>)
+        general = !((int32_t)len >= p.maxg && (int32_t)len <= 64 * kSub);
     // lane runs: the layout is decided before any window is loaded (the
     // eligibility is wave-uniform: direct tables present = the split path)
     bool runs_done = false;
@@ -2183,9 +2300,23 @@ __global__ __launch_bounds__(kScoreWaves * 64, kScoreMinWgPerCu * kScoreWaves / 
         __builtin_amdgcn_wave_barrier();
         if (staged) {
             for (int i = 0; i < cnt;) {
-                const int64_t b = rdlane_i64(offv, i);
-                const int64_t len = rdlane_i64(offv, i + 1) - b;
-                const DocSrc src{cur, b - s0};
+                int64_t b, len, base;
+                if constexpr (LDGPU_RUN_GEOM32 && kLaneRuns<MODE, true, BL, WIDE>) {
+                    // 32-bit geometry: s0 <= b <= b + len <= send and
+                    // send - s0 <= kBufBytes in a staged group, so b - s0 and
+                    // len lie in [0, kBufBytes] and are exact from the offsets'
+                    // low halves alone -- two v_readlane and scalar 32-bit
+                    // arithmetic, no 64-bit compare on the vector unit
+                    const uint32_t blo = rdlane((uint32_t)offv, i);
+                    len = (int64_t)(int32_t)(rdlane((uint32_t)offv, i + 1) - blo);
+                    base = (int64_t)(int32_t)(blo - (uint32_t)s0);
+                    b = s0 + base;
+                } else {
+                    b = rdlane_i64(offv, i);
+                    len = rdlane_i64(offv, i + 1) - b;
+                    base = b - s0;
+                }
+                const DocSrc src{cur, base};
                 if constexpr (PACK) {
                     // a pack of consecutive short documents (score_pack);
                     // packing runs only without score output, with count
