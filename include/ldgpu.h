@@ -245,6 +245,61 @@ int ldgpu_score_spans_device(ldgpu_model* model, const uint8_t* d_bytes, int64_t
                              const int64_t* d_span_offsets, int64_t n_spans,
                              int32_t* d_labels, double* d_scores, void* stream);
 
+/* Segment form of SCORE: the span labels of every document smoothed by a best
+ * path over its spans with a cost per language change, computed on the device
+ * (only the [n_spans] labels leave it; the score matrix never exists).  The
+ * reference has no such output.  Spans, their numbering and their score rows
+ * s_j[0 .. n_langs) are exactly those of ldgpu_score_spans; penalty is an
+ * fp64 >= 0 (+inf allowed; negative or NaN is LDGPU_EINVAL) in score units --
+ * a span's score is a sum of log(1 + 1/k) per hit window.  The rule, for a
+ * document's spans 0 .. n-1 (L = n_langs):
+ *   first_max(v):  m = v[0], a = 0;
+ *                  for l = 1 .. L-1: if (v[l] > m) { m = v[l]; a = l; }  -> (m, a)
+ *   dp_0[l]    = s_0[l]
+ *   (m_j, a_j) = first_max(dp_j)
+ *   for j >= 1, with t = m_{j-1} - penalty (one fp64 subtraction):
+ *     switch_j[l] = (t > dp_{j-1}[l])      (a tie stays; any comparison with a NaN stays)
+ *     dp_j[l]     = s_j[l] + (switch_j[l] ? t : dp_{j-1}[l])      (one fp64 addition)
+ *   y_{n-1} = a_{n-1};   y_{j-1} = switch_j[y_j] ? a_{j-1} : y_j   for j = n-1 .. 1
+ * y_j is span j's label.  All comparisons are plain IEEE `>`; no multiply
+ * appears, so nothing contracts into an FMA; the result is defined for every
+ * input, +-inf and NaN rows included.  first_max is breeze's first maximum (the
+ * label rule of ldgpu_score, entry 0 of the top-k order): a document of one
+ * span gets exactly the label ldgpu_score_spans gives it, an empty document's
+ * single empty span gets 0.  With penalty = +inf no span ever switches: a
+ * document gets one label throughout.  With penalty = 0 every span may switch
+ * for free.
+ * Parallelism is one wave per document: a call on a few very long documents
+ * is serial in their spans.
+ *
+ * Host buffers in and out; synchronous and thread-safe as ldgpu_score.
+ * out_labels [n_spans], n_spans = span_offsets[n_docs] of ldgpu_span_offsets.
+ * Argument checks, LDGPU_EROWLEN, the pipeline over pinned / pageable buffers
+ * and the absent document-length limit are those of ldgpu_score_spans.  The
+ * pipeline's chunks end at document boundaries (a document's labels are known
+ * only after its last span): as many whole documents as fit the span call's
+ * span budget and 64 MiB of source bytes, one document at least; a single
+ * document beyond the budget is a chunk of its own, cut into span chunks by
+ * the device form's loop. */
+int ldgpu_score_segments(ldgpu_model* model, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs,
+                         int32_t width, int32_t stride, double penalty, int32_t* out_labels /* [n_spans] */);
+
+/* Device-resident variant, asynchronous on `stream` under the rules and
+ * argument checks of ldgpu_score_spans_device (d_span_offsets, n_spans and its
+ * over-estimate as there: a span index at or beyond d_span_offsets[n_docs]
+ * gets label 0), plus the penalty check.  The spans are gathered and scored
+ * in chunks as there (each additionally bounded by the top-k call's 256 MiB of
+ * scores), every chunk's rows consumed from stream-ordered scratch by the
+ * forward pass, with the open document's dp row carried to the next chunk;
+ * one backtrace pass follows the last chunk.  Whole-call scratch, also
+ * stream-ordered: n_spans * (8 * ceil(n_langs / 64) + 4) bytes of switch words
+ * and first-maximum indices, plus two carry rows of n_langs doubles; a failed
+ * allocation is LDGPU_ENOMEM and names the size.  Nothing is read back. */
+int ldgpu_score_segments_device(ldgpu_model* model, const uint8_t* d_bytes, int64_t n_bytes,
+                                const int64_t* d_offsets, int64_t n_docs, int32_t width, int32_t stride,
+                                double penalty, const int64_t* d_span_offsets, int64_t n_spans,
+                                int32_t* d_labels, void* stream);
+
 /* -------------------------------------------------------------------- FIT */
 typedef struct ldgpu_counts ldgpu_counts;
 

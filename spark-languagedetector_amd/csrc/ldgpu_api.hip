@@ -2505,6 +2505,155 @@ extern "C" int ldgpu_score_spans(ldgpu_model* m, const uint8_t* bytes, const int
     return with_pipe(m, [&](ScorePipe* pp) { return run_score_pipe(m, pp, call, cut, launch); });
 }
 
+// ---------------------------------------------------------- SCORE: segments
+// Span labels smoothed by a best path with a cost per language change (the
+// rule: include/ldgpu.h; the kernels: ldgpu_segments.hip).
+namespace {
+int check_penalty(double penalty) {
+    if (!(penalty >= 0.0)) return fail(LDGPU_EINVAL, "segment penalty = %g: it must be >= 0 (+inf allowed)", penalty);
+    return LDGPU_OK;
+}
+
+// The smoothed labels of the spans [0, n_spans) of the corpus sp describes
+// (sp.g0 / sp.nc are set here) to d_labels [n_spans], queued on st: span
+// chunks scored into stream-ordered scratch (span_chunk) and consumed there by
+// the forward kernel, the two carry rows alternating by chunk parity, then one
+// backtrace.  The device form runs it on the caller's arrays, the host form on
+// a stage's buffers.
+int segments_launch(ldgpu_model* m, SpanParams sp, double penalty, int64_t n_spans, int32_t* d_labels, int32_t* d_err,
+                    hipStream_t st) {
+    if (n_spans <= 0) return LDGPU_OK;
+    const int64_t L = m->L, W = (L + 63) / 64;
+    // switch words, first-maximum indices, two carry rows: 64-bit arithmetic
+    const int64_t per_span = 8 * W + 4, n_carry = 2 * 8 * L;
+    if (n_spans > (INT64_MAX - n_carry - 512) / per_span)
+        return fail(LDGPU_ENOMEM, "segment scratch for %lld spans of %lld languages exceeds 2^63 bytes",
+                    (long long)n_spans, (long long)L);
+    const size_t n_sw = up256((size_t)n_spans * 8 * (size_t)W), n_arg = up256((size_t)n_spans * 4);
+    const size_t whole = n_sw + n_arg + (size_t)n_carry;
+    char* scratch = nullptr;
+    if (hipMallocAsync((void**)&scratch, whole, st) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(LDGPU_ENOMEM, "segment scratch of %llu bytes (%lld spans)", (unsigned long long)whole,
+                    (long long)n_spans);
+    }
+    SegmentParams g{};
+    g.span_offsets = sp.span_offsets;
+    g.n_docs = sp.n_docs;
+    g.n_spans = n_spans;
+    g.L = m->L;
+    g.penalty = penalty;
+    g.sw = (uint64_t*)scratch;
+    g.arg = (int32_t*)(scratch + n_sw);
+    double* carry = (double*)(scratch + n_sw + n_arg);
+    g.labels = d_labels;
+    const int64_t chunk = std::min(span_chunk_spans(sp.width), topk_chunk_docs(m->L));
+    int rc = LDGPU_OK;
+    hipError_t e = hipSuccess;
+    int64_t k = 0;
+    for (int64_t g0 = 0; g0 < n_spans && !rc && e == hipSuccess; g0 += chunk, ++k) {
+        const int64_t nc = std::min(chunk, n_spans - g0);
+        const size_t score_bytes = sizeof(double) * (size_t)nc * (size_t)L;
+        char* cs = nullptr;  // the chunk's score rows, then its raw labels (score_launch's own)
+        if (hipMallocAsync((void**)&cs, score_bytes + sizeof(int32_t) * (size_t)nc, st) != hipSuccess) {
+            (void)hipGetLastError();
+            rc = fail(LDGPU_ENOMEM, "segment chunk scratch of %llu bytes",
+                      (unsigned long long)(score_bytes + sizeof(int32_t) * (size_t)nc));
+            break;
+        }
+        sp.g0 = g0;
+        sp.nc = nc;
+        rc = span_chunk(m, sp, (int32_t*)(cs + score_bytes), (double*)cs, d_err, st);
+        if (!rc) {
+            g.scores = (const double*)cs;
+            g.g0 = g0;
+            g.nc = nc;
+            g.carry_in = carry + (k & 1) * L;
+            g.carry_out = carry + ((k + 1) & 1) * L;
+            e = launch_segment_forward(g, m->ctx->cus, st);
+        }
+        (void)hipFreeAsync(cs, st);
+    }
+    if (!rc && e == hipSuccess) e = launch_segment_backtrace(g, m->ctx->cus, st);
+    (void)hipFreeAsync(scratch, st);
+    if (rc) return rc;
+    HIP_TRY(e);
+    return LDGPU_OK;
+}
+}  // namespace
+
+extern "C" int ldgpu_score_segments_device(ldgpu_model* m, const uint8_t* d_bytes, int64_t n_bytes,
+                                           const int64_t* d_offsets, int64_t n_docs, int32_t width, int32_t stride,
+                                           double penalty, const int64_t* d_span_offsets, int64_t n_spans,
+                                           int32_t* d_labels, void* stream) {
+    const bool null_ptr = n_spans > 0 && (!d_offsets || !d_span_offsets || !d_labels || (n_bytes > 0 && !d_bytes));
+    if (int rc = device_call_begin(m, n_docs, d_bytes, null_ptr, [&] {
+            if (n_spans < 0) return fail(LDGPU_EINVAL, "n_spans < 0");
+            if (int r = check_span_args(width, stride)) return r;
+            return check_penalty(penalty);
+        }))
+        return rc;
+    hipStream_t st = (hipStream_t)stream;
+    SpanParams sp{};
+    sp.bytes = d_bytes;
+    sp.n_bytes = n_bytes;
+    sp.offsets = d_offsets;
+    sp.n_docs = n_docs;
+    sp.span_offsets = d_span_offsets;
+    sp.width = width;
+    sp.stride = stride;
+    if (int rc = segments_launch(m, sp, penalty, n_spans, d_labels, m->d_err, st)) return rc;
+    if (n_spans > 0) {
+        if (int rc = check_row_error(m, m->d_err, st)) return rc;
+    }
+    return ok();
+}
+
+// The segment form of the host pipeline (run_score_pipe).  A document's labels
+// are known only after its last span, and the pipeline hands a chunk's outputs
+// back when the chunk retires: so, unlike the span form's, a chunk ends at a
+// document boundary -- as many whole documents as fit the span budget
+// (span_chunk_spans) and kScoreChunkBytes of source bytes, one at least.  A
+// single document beyond the budget is a chunk of its own, which
+// segments_launch cuts into span chunks with carry.
+extern "C" int ldgpu_score_segments(ldgpu_model* m, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs,
+                                    int32_t width, int32_t stride, double penalty, int32_t* out_labels) {
+    // (no document-length limit, as in the span form)
+    if (int rc = check_host_call(m, bytes, offsets, n_docs, out_labels, "out_labels", false, [&] {
+            if (int r = check_span_args(width, stride)) return r;
+            return check_penalty(penalty);
+        }))
+        return rc;
+    if (n_docs == 0) return ok();
+    std::vector<int64_t> soff((size_t)n_docs + 1);
+    host_span_offsets(offsets, n_docs, width, stride, soff.data());
+    const int64_t n_spans = soff[n_docs];
+    const ScoreCall call{bytes, offsets, n_docs, soff.data(), n_spans,
+                         {{&ScoreStage::labels, &ScoreStage::h_labels, out_labels, sizeof(int32_t)},
+                          {&ScoreStage::scores, &ScoreStage::h_scores, nullptr, 0}}};
+    const int64_t budget = span_chunk_spans(width);
+    // (a chunk starts at a document's first span: g0 is one of soff)
+    auto cut = [&](int64_t g0) {
+        const int64_t d0 = (int64_t)(std::upper_bound(soff.begin(), soff.begin() + n_docs, g0) - soff.begin()) - 1;
+        int64_t d1 = d0 + 1;
+        while (d1 < n_docs && soff[d1 + 1] - soff[d0] <= budget && offsets[d1 + 1] - offsets[d0] <= kScoreChunkBytes)
+            ++d1;
+        return PipeChunk{soff[d0], soff[d1], offsets[d0], offsets[d1], d0, d1 - d0};
+    };
+    auto launch = [&](ScoreStage& st, const PipeChunk& ch, int32_t* d_err) -> int {
+        SpanParams sp{};
+        sp.bytes = (const uint8_t*)st.bytes.p;
+        sp.n_bytes = ch.hi - ch.lo;
+        sp.offsets = (const int64_t*)st.offsets.p;
+        sp.n_docs = ch.n_docs;
+        sp.span_offsets = sp.offsets + ch.n_docs + 1;
+        sp.width = width;
+        sp.stride = stride;
+        return segments_launch(m, sp, penalty, ch.i1 - ch.i0, (int32_t*)st.labels.p, d_err, st.stream);
+    };
+    return with_pipe(m, [&](ScorePipe* pp) { return run_score_pipe(m, pp, call, cut, launch); });
+}
+
 // ---------------------------------------------------------------------- FIT
 struct ldgpu_counts {
     ldgpu_ctx* ctx = nullptr;

@@ -273,6 +273,28 @@ hipError_t launch_span_offsets(const int64_t* offsets, int64_t n_docs, int32_t w
                                int64_t* span_offsets, void* scan_tmp, size_t scan_bytes, int cus, hipStream_t stream);
 // geometry (src, len), the scan into coff, the gather into out
 hipError_t launch_span_gather(const SpanParams& p, void* scan_tmp, size_t scan_bytes, int cus, hipStream_t stream);
+// Smoothed span labels (ldgpu_segments.hip; the rule of ldgpu_score_segments,
+// include/ldgpu.h): a best path over every document's spans with a cost per
+// language change.  The forward kernel runs once per scored chunk of spans
+// (one wave per document with a span in it) and leaves, per span, the switch
+// bits of every language and the first maximum's index; the backtrace kernel
+// runs once after the last chunk and writes the labels.
+struct SegmentParams {
+    const double* scores;         // forward: the chunk's score rows [nc][L]
+    const int64_t* span_offsets;  // [n_docs + 1]
+    int64_t n_docs;
+    int64_t g0, nc;               // forward: the chunk's spans
+    int64_t n_spans;              // the call's spans (sw, arg and labels hold this many)
+    int32_t L;
+    double penalty;
+    uint64_t* sw;                 // [n_spans][ceil(L / 64)]: bit l of span j = switch_j[l]
+    int32_t* arg;                 // [n_spans]: a_j
+    const double* carry_in;       // [L]: dp of the document that enters the chunk
+    double* carry_out;            // [L]: dp of the document that leaves it (another row)
+    int32_t* labels;              // backtrace: out [n_spans]
+};
+hipError_t launch_segment_forward(const SegmentParams& p, int cus, hipStream_t stream);
+hipError_t launch_segment_backtrace(const SegmentParams& p, int cus, hipStream_t stream);
 // sets the dynamic-LDS limit and returns the resident workgroups per CU
 // (chunks: a count-mode table's keyed bloom in the chunk layout)
 hipError_t score_prepare(int slices, int mode, bool lds_bloom, bool chunks, size_t lds_bytes, int* blocks_per_cu);

@@ -72,6 +72,9 @@ SIGNATURES = [
     ("ldgpu_span_offsets_device", ctypes.c_int, [_p, _p, _i64, _i32, _i32, _p, _p]),
     ("ldgpu_score_spans", ctypes.c_int, [_p, _p, _p, _i64, _i32, _i32, _p, _p]),
     ("ldgpu_score_spans_device", ctypes.c_int, [_p, _p, _i64, _p, _i64, _i32, _i32, _p, _i64, _p, _p, _p]),
+    ("ldgpu_score_segments", ctypes.c_int, [_p, _p, _p, _i64, _i32, _i32, ctypes.c_double, _p]),
+    ("ldgpu_score_segments_device", ctypes.c_int,
+     [_p, _p, _i64, _p, _i64, _i32, _i32, ctypes.c_double, _p, _i64, _p, _p]),
     ("ldgpu_counts_create", ctypes.c_int, [_p, _i32, _p, _i32, _i64, _pp]),
     ("ldgpu_counts_destroy", ctypes.c_int, [_p]),
     ("ldgpu_counts_langs", ctypes.c_int, [_p, _pi32]),
@@ -207,7 +210,8 @@ def device_count() -> int:
 # the sources the library is built from, in the Makefile's PROV order
 _PROV = ["csrc/ldgpu_api.hip", "csrc/ldgpu_score.hip", "csrc/ldgpu_fit.hip", "csrc/ldgpu_general.hip",
          "csrc/ldgpu_long.hip", "csrc/ldgpu_replay.hip", "csrc/ldgpu_pre.hip", "csrc/ldgpu_topk.hip",
-         "csrc/ldgpu_spans.hip", "csrc/ldgpu_common.h", "csrc/ldgpu_internal.h", "csrc/ldgpu_fit.h", "../include/ldgpu.h"]
+         "csrc/ldgpu_spans.hip", "csrc/ldgpu_segments.hip", "csrc/ldgpu_common.h", "csrc/ldgpu_internal.h",
+         "csrc/ldgpu_wave.h", "csrc/ldgpu_fit.h", "../include/ldgpu.h"]
 
 
 def tree_source_hash() -> str:

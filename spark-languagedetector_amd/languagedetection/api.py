@@ -205,6 +205,43 @@ class LanguageDetectorModel(_Params):
         out[outputCol] = pd.Series(found, index=out.index, dtype=object)
         return out
 
+    # The same runs from span labels smoothed on the GPU by a best path with a
+    # cost per language change (the rule: languagedetection.segments).
+    def predict_segments(self, texts: Sequence[str], width: int, stride: int, penalty: float
+                         ) -> List[List[Tuple[int, int, str]]]:
+        """Per text its runs (start, end, language) as predict_spans gives
+        them, from the smoothed span labels: `penalty` (score units, >= 0) is
+        what a change of language between two spans costs."""
+        for t in texts:
+            if t is None:
+                raise NullPointerException("text is null")
+        data, offsets = encoding.pack_score(texts)
+        labels, soff = self.device_model().score_segments(data, offsets, width, stride, penalty)
+        out = []
+        for d in range(len(texts)):
+            r = spans.runs(int(offsets[d + 1] - offsets[d]), labels[soff[d]:soff[d + 1]], width, stride)
+            out.append([(a, b, self.supportedLanguages[lab]) for a, b, lab in r])
+        return out
+
+    def transformSegments(self, dataset, width: int, stride: int, penalty: float, outputCol: str = "langSegments"):
+        """Append outputCol (the row's smoothed runs as a list of (start, end,
+        language)); an existing column of that name is rejected as
+        transformSchema rejects outputCol."""
+        import pandas as pd
+        df = dataset if isinstance(dataset, pd.DataFrame) else pd.DataFrame(dataset)
+        schema = self._schema_of(df)
+        in_type = schema.get(self.getInputCol())
+        if in_type is None:
+            raise ValueError(f"Field \"{self.getInputCol()}\" does not exist.")
+        if in_type != "string":
+            raise ValueError(f"requirement failed: Input type must be StringType but got {in_type}.")
+        if outputCol in schema:
+            raise ValueError(f"requirement failed: Column {outputCol} already exists.")
+        found = self.predict_segments(list(df[self.getInputCol()]), width, stride, penalty)
+        out = df.copy()
+        out[outputCol] = pd.Series(found, index=out.index, dtype=object)
+        return out
+
     # persistence (LanguageDetectorModel.scala:24-105): the reference's layout
     def write(self) -> "LanguageDetectorModelWriter":
         return LanguageDetectorModelWriter(self)

@@ -229,6 +229,36 @@ class DeviceModel(_Owner):
                                                       ctypes.c_void_p(d_scores) if d_scores else None,
                                                       ctypes.c_void_p(st) if st else None))
 
+    # Smoothed span labels (an addition; the rule: languagedetection.segments)
+    def score_segments(self, data: np.ndarray, offsets: np.ndarray, width: int, stride: int, penalty: float,
+                       out_labels: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """Host buffers -> (labels int32[n_spans], span_offsets int64[n_docs +
+        1]): the span labels of score_spans smoothed on the device by a best
+        path with `penalty` (score units, >= 0, inf allowed) per language
+        change (ldgpu_score_segments).  `out_labels` (e.g. a PinnedArray's
+        array) receives the labels."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        soff = self.span_offsets(offsets, width, stride)
+        n = int(soff[-1])
+        labels = np.zeros(n, dtype=np.int32) if out_labels is None else out_labels
+        assert labels.dtype == np.int32 and labels.shape == (n,) and labels.flags.c_contiguous
+        self._check(self.lib.ldgpu_score_segments(self.h, _ptr(data), _ptr(offsets), len(offsets) - 1, int(width),
+                                                  int(stride), float(penalty), _ptr(labels)))
+        return labels, soff
+
+    def score_segments_device(self, d_bytes: int, n_bytes: int, d_offsets: int, n_docs: int, width: int, stride: int,
+                              penalty: float, d_span_offsets: int, n_spans: int, d_labels: int,
+                              stream: Optional[int] = None) -> None:
+        """Device pointers -> the [n_spans] smoothed labels in place, async on
+        `stream` as score_device (ldgpu_score_segments_device)."""
+        st = self.stream() if stream is None else stream
+        self._check(self.lib.ldgpu_score_segments_device(self.h, ctypes.c_void_p(d_bytes), n_bytes,
+                                                         ctypes.c_void_p(d_offsets), n_docs, int(width), int(stride),
+                                                         float(penalty), ctypes.c_void_p(d_span_offsets), n_spans,
+                                                         ctypes.c_void_p(d_labels),
+                                                         ctypes.c_void_p(st) if st else None))
+
 
 class DeviceCounts(_Owner):
     """A (gram, language) -> count table on one GPU (computeGrams + reduceGrams)."""
