@@ -138,6 +138,9 @@ int ldgpu_model_info(const ldgpu_model* model, int32_t* mode, int64_t* n_keys,
                                                   of 3 and 4 bytes verified from a second table of 8-byte
                                                   slots (no key of 5 bytes or more, one language per such
                                                   row) */
+#define LDGPU_LAYOUT_TRIE               0x1000 /* count mode, labels-only calls on documents that are not
+                                                  packed: every key (at most 4 bytes, one language each) in
+                                                  an exact byte trie held in LDS; no filter, queue or verify */
 int ldgpu_model_layout(const ldgpu_model* model, int32_t* flags);
 /* The model's language count (a caller sizing score buffers, e.g. the JNI
  * shim, takes it from the model rather than trusting its own). */

@@ -622,6 +622,15 @@ struct ldgpu_model {
     uint64_t wslot_cap = 0;
     NarrowSlot* d_nslots = nullptr;  // order-free modes: the keys of 3 and 4 bytes in 8-byte slots, nullptr: none
     uint64_t nslot_cap = 0;
+    // count mode on the exact LDS trie (ldgpu_trie.h / ldgpu_trie.hip), nullptr:
+    // the table is not eligible
+    uint32_t* d_trie = nullptr;
+    uint32_t trie_words = 0, trie_dead = 0;
+    int trie_max_len = 0;
+    int trie_wg_per_cu = 1;
+    // the lists of the documents the trie kernel leaves: stream-ordered scratch
+    // from a pool of the model's own that keeps its blocks across synchronises
+    hipMemPool_t trie_pool = nullptr;
     Bucket* d_buckets = nullptr;  // count mode key table
     uint64_t n_buckets = 0;
     uint32_t* d_filter = nullptr;
@@ -676,7 +685,8 @@ void model_free(ldgpu_model* m) {
                             "store-loop iterations %llu\n", st[0], st[1], st[2], st[3]);
         (void)hipFree(m->d_stats);
     }
-    for (void* p : {(void*)m->d_slots, (void*)m->d_wslots, (void*)m->d_nslots, (void*)m->d_buckets, (void*)m->d_filter, (void*)m->d_masks, (void*)m->d_vals, (void*)m->d_rows,
+    if (m->trie_pool) (void)hipMemPoolDestroy(m->trie_pool);
+    for (void* p : {(void*)m->d_slots, (void*)m->d_wslots, (void*)m->d_nslots, (void*)m->d_trie, (void*)m->d_buckets, (void*)m->d_filter, (void*)m->d_masks, (void*)m->d_vals, (void*)m->d_rows,
                     (void*)m->d_fold, (void*)m->d_err, (void*)m->d_gslots, (void*)m->d_arena, (void*)m->d_koff,
                     (void*)m->d_lbits})
         if (p) (void)hipFree(p);
@@ -1644,7 +1654,53 @@ int model_build(ldgpu_ctx* ctx, int32_t n_langs, const int32_t* gram_lengths, in
         }
     }
 
+    // The exact LDS trie (ldgpu_trie.h): a count-mode table whose keys all have
+    // at most kTrieMaxLen bytes, name exactly one language below kTrieMaxLangs
+    // and are no wrong-length rows, when its packed image and the per-wave areas
+    // leave two workgroups per CU resident.  Labels-only calls on documents
+    // that are not packed then walk the trie (score_launch); the model keeps
+    // everything above, which serves every other call.  Terminals only for the
+    // lengths gramLengths lists.  Diagnostics: LDGPU_NO_TRIE=1.
+    TrieImage trie;
+    {
+        bool eligible = m->mode == 3 && m->count_int_argmax && nw == 0 && n_langs <= (int)kTrieMaxLangs && nn > 0;
+        if (const char* s = diag_env("LDGPU_NO_TRIE")) eligible &= atoi(s) == 0;
+        uint32_t listed = 0;
+        for (int i = 0; i < n_grams; ++i)
+            if (gram_lengths[i] >= 1 && gram_lengths[i] <= kTrieMaxLen) listed |= 1u << gram_lengths[i];
+        constexpr uint32_t kWgLds = 163840 / 2;
+        const uint32_t per_wave = trie_lds_bytes(0, S, kScoreWaves, kBufWords);
+        // (more keys than slots: rejected before a key is copied or a node built)
+        if (eligible) eligible = per_wave + 4u * 512u <= kWgLds && (uint64_t)nn <= (kWgLds - per_wave) / 4u;
+        std::vector<TrieKey> tkeys;
+        for (int64_t i = 0; i < nn && eligible; ++i) {
+            const int len = key_len(keys[i]);
+            int bits = 0;
+            uint32_t lang = 0;
+            for (int s = 0; s < S; ++s) {
+                const uint64_t w = masks[(size_t)i * S + s];
+                if (w && !bits) lang = 64u * (uint32_t)s + (uint32_t)__builtin_ctzll(w);
+                bits += __builtin_popcountll(w);
+            }
+            if (len < 1 || len > kTrieMaxLen || bits != 1 || t.bad[i]) {
+                eligible = false;
+                break;
+            }
+            tkeys.push_back(TrieKey{(uint32_t)keys[i], (uint8_t)len,
+                                    (uint8_t)(((listed >> len) & 1u) ? lang : kTrieNoLang)});
+        }
+        if (eligible) eligible = trie_build(tkeys, (kWgLds - per_wave) / 4u, trie);
+        if (eligible && trie.max_len < 1) eligible = false;  // (no counted key: nothing to walk)
+        if (!eligible) trie.words.clear();
+    }
+
     hipError_t e = hipSetDevice(ctx->device);
+    if (e == hipSuccess && !trie.words.empty()) {
+        e = upload(&m->d_trie, trie.words, &m->device_bytes);
+        m->trie_words = (uint32_t)trie.words.size();
+        m->trie_dead = trie.dead;
+        m->trie_max_len = trie.max_len;
+    }
     if (e == hipSuccess) e = upload(&m->d_slots, slots, &m->device_bytes);
     if (e == hipSuccess && nw > 0) e = upload(&m->d_wslots, wslots, &m->device_bytes);
     if (e == hipSuccess && !nslots.empty()) e = upload(&m->d_nslots, nslots, &m->device_bytes);
@@ -1683,6 +1739,26 @@ int model_build(ldgpu_ctx* ctx, int32_t n_langs, const int32_t* gram_lengths, in
     // persistent grid = what is resident; never more workgroups than the LDS admits
     m->wg_per_cu = std::max<int>(1, std::min<int>(resident > 0 ? resident : 1, (int)(163840 / m->lds_bytes)));
     if (const char* ov = diag_env("LDGPU_WG_PER_CU")) m->wg_per_cu = std::max(1, atoi(ov));
+    if (m->d_trie && e == hipSuccess) {
+        const size_t tl = trie_lds_bytes(m->trie_words, S, kScoreWaves, kBufWords);
+        int r = 0;
+        e = trie_prepare(S, m->trie_max_len, tl, &r);
+        m->trie_wg_per_cu = std::max<int>(1, std::min<int>(r > 0 ? r : 1, (int)(163840 / tl)));
+        // The default pool releases its blocks at every synchronise, so a host
+        // pipeline that synchronises per chunk paid an allocation and a release
+        // for every chunk's list; this pool keeps them (its high-water mark is
+        // 8 B per document of the largest call in flight).
+        if (e == hipSuccess) {
+            hipMemPoolProps props{};
+            props.allocType = hipMemAllocationTypePinned;
+            props.handleTypes = hipMemHandleTypeNone;
+            props.location.type = hipMemLocationTypeDevice;
+            props.location.id = ctx->device;
+            e = hipMemPoolCreate(&m->trie_pool, &props);
+            uint64_t keep = UINT64_MAX;
+            if (e == hipSuccess) e = hipMemPoolSetAttribute(m->trie_pool, hipMemPoolAttrReleaseThreshold, &keep);
+        }
+    }
     if (const char* ab = diag_env("LDGPU_ABLATE")) m->ablate = atoi(ab);
     if (diag_env("LDGPU_STATS") && e == hipSuccess) {
         e = hipMalloc((void**)&m->d_stats, 4 * sizeof(unsigned long long));
@@ -1690,9 +1766,9 @@ int model_build(ldgpu_ctx* ctx, int32_t n_langs, const int32_t* gram_lengths, in
     }
     if (diag_env("LDGPU_DEBUG"))
         fprintf(stderr, "[ldgpu] model: keys=%lld mode=%d direct=%u slices=%d bloom_words=%llu lds_bloom=%d lds=%zu B "
-                        "resident_api=%d wg_per_cu=%d pack=%d classes=%d\n",
+                        "resident_api=%d wg_per_cu=%d pack=%d classes=%d trie_words=%u trie_wg_per_cu=%d\n",
                 (long long)nk, m->mode, m->direct_words, S, (unsigned long long)bwords, (int)m->lds_filter, m->lds_bytes, resident,
-                m->wg_per_cu, (int)m->pack_ok, m->n_cls);
+                m->wg_per_cu, (int)m->pack_ok, m->n_cls, m->trie_words, m->trie_wg_per_cu);
     if (e != hipSuccess) {
         model_free(m);
         return fail(e == hipErrorOutOfMemory ? LDGPU_ENOMEM : LDGPU_EDEVICE, "model upload: %s",
@@ -1737,6 +1813,7 @@ extern "C" int ldgpu_model_layout(const ldgpu_model* m, int32_t* flags) {
     if (b->d_buckets) f |= LDGPU_LAYOUT_BUCKETS;
     if (b->d_wslots) f |= LDGPU_LAYOUT_WIDE_KEYS;
     if (b->d_nslots) f |= LDGPU_LAYOUT_NARROW_SLOTS;
+    if (b->d_trie) f |= LDGPU_LAYOUT_TRIE;
     if (b->direct_words) f |= LDGPU_LAYOUT_DIRECT;
     if (b->pack_ok) f |= LDGPU_LAYOUT_PACKS;
     if (b->n_cls && m->blocks.empty()) f |= LDGPU_LAYOUT_CLASSES;
@@ -1803,6 +1880,49 @@ int class_replay(ldgpu_model* m, const ScoreParams& p4, hipStream_t st) {
         p1.nslots = nullptr;
         gram_lists(m, p1, 1);
         e = launch_score(p1, m->slices, 1, m->lds_filter, score_grid(m, n), st);
+    }
+    (void)hipFreeAsync(idx, st);
+    HIP_TRY(e);
+    return LDGPU_OK;
+}
+
+// count mode on the exact LDS trie (ldgpu_trie.hip), then the documents it
+// left, listed in stream-ordered scratch of the worst case (every document)
+// from the model's pool
+int trie_launch(ldgpu_model* m, const ScoreParams& p, hipStream_t st) {
+    const int64_t n = p.n_docs;
+    int64_t* idx = nullptr;
+    HIP_TRY(hipMallocFromPoolAsync((void**)&idx, sizeof(int64_t) * (size_t)(n + 1), m->trie_pool, st));
+    unsigned long long* d_k = (unsigned long long*)(idx + n);
+    hipError_t e = hipMemsetAsync(d_k, 0, sizeof *d_k, st);
+    if (e == hipSuccess) {
+        TrieParams t{};
+        t.bytes = p.bytes;
+        t.n_bytes = p.n_bytes;
+        t.offsets = p.offsets;
+        t.n_docs = n;
+        t.group = p.group;
+        t.labels = p.labels;
+        t.image = m->d_trie;
+        t.image_words = m->trie_words;
+        t.dead = m->trie_dead;
+        t.L = m->L;
+        t.count_sign = m->count_sign;
+        t.maxg = p.maxg;
+        for (int d = 1; d <= kTrieMaxLen; ++d) t.mult[d] = ((p.fast_mask >> d) & 1u) ? p.mult[d] : 0u;
+        t.left = idx;
+        t.n_left = d_k;
+        int grid = (int)std::max<int64_t>(
+            1, std::min<int64_t>((n + kScoreWaves - 1) / kScoreWaves, (int64_t)m->ctx->cus * m->trie_wg_per_cu));
+        if (const char* g = diag_env("LDGPU_SCORE_GRID")) grid = std::max(1, atoi(g));
+        e = launch_trie(t, m->slices, m->trie_max_len, grid, st);
+    }
+    if (e == hipSuccess) {
+        ScoreParams pi = p;
+        pi.doc_idx = idx;
+        pi.n_docs_dev = d_k;
+        pi.pack = 0;
+        e = launch_score(pi, m->slices, 3, m->lds_filter, score_grid(m, n), st);
     }
     (void)hipFreeAsync(idx, st);
     HIP_TRY(e);
@@ -1965,6 +2085,15 @@ int score_launch(ldgpu_model* m, const uint8_t* d_bytes, int64_t n_bytes, const 
     // count mode, labels only: a fast-path document (<= 256 B, so far below
     // count_argmax_len) takes the count argmax (score kernel kFmArgmax)
     if (mode == 3 && p.count_argmax_len >= 256 && !d_scores && !d_best) p.fast_mask |= 1u << 17;
+    // The exact LDS trie: a labels-only count-mode call (kFmArgmax's condition)
+    // that would not pack.  The documents the trie kernel does not score
+    // (shorter than maxg, longer than 256 bytes, unstaged groups) come back
+    // listed, their count on the device, and an indirect launch of the kernel
+    // above scores them in place on the same stream: nothing is read back, and
+    // with none listed that launch leaves at once.
+    // (the diagnostics build's ablations and statistics are the kernel's above)
+    if (m->d_trie && mode == 3 && ((p.fast_mask >> 17) & 1u) && !p.pack && !m->ablate && !m->d_stats)
+        return trie_launch(m, p, st);
     HIP_TRY(launch_score(p, m->slices, mode, m->lds_filter, score_grid(m, n_docs), st));
     if (classes) return class_replay(m, p, st);
     return LDGPU_OK;

@@ -3,6 +3,7 @@
 #pragma once
 
 #include "ldgpu_common.h"
+#include "ldgpu_trie.h"
 
 // Diagnostics build (lib/libldgpu_diag.so, -DLDGPU_DIAG=1): only there does
 // the library read the LDGPU_* environment switches (path selection for tests,
@@ -171,6 +172,32 @@ LDGPU_SCORE_PAIR_DECL(4, 1) LDGPU_SCORE_PAIR_DECL(4, 2) LDGPU_SCORE_PAIR_DECL(4,
 // documents labelled -1 (then replayed by an indirect mode-1 launch)
 hipError_t launch_amb_compact(const int32_t* labels, int64_t n, int64_t* idx, unsigned long long* n_out,
                               hipStream_t stream);
+
+// Count mode on an exact LDS trie (ldgpu_trie.hip; the image: ldgpu_trie.h):
+// labels only, documents of maxg..256 bytes in staged groups; every other
+// document gets label -1 and is listed in left[0 .. *n_left) for an indirect
+// launch of score_kernel (mode 3, doc_idx = left).
+struct TrieParams {
+    const uint8_t* bytes;       // 4-byte aligned
+    int64_t n_bytes;            // readable bytes of `bytes`
+    const int64_t* offsets;     // [n_docs + 1]
+    int64_t n_docs;
+    int32_t group;              // documents per staged group (1..63)
+    int32_t* labels;            // [n_docs]
+    const uint32_t* image;      // the trie image (TrieImage::words)
+    uint32_t image_words;       // a multiple of 4
+    uint32_t dead;              // the dead entry
+    int32_t L;
+    int32_t count_sign;         // sign of the table's one value
+    int32_t maxg;               // max(G)
+    uint32_t mult[kTrieMaxLen + 1];  // multiplicity of n in G; 0: n is not listed or has no key
+    int64_t* left;              // out: the documents left to score_kernel ([n_docs])
+    unsigned long long* n_left; // out: their count (zeroed by the caller)
+};
+// slices = ceil(L / 64), max_len = the longest counted key (1..kTrieMaxLen)
+hipError_t launch_trie(const TrieParams& p, int slices, int max_len, int grid, hipStream_t stream);
+// sets the dynamic-LDS limit and returns the resident workgroups per CU
+hipError_t trie_prepare(int slices, int max_len, size_t lds_bytes, int* blocks_per_cu);
 
 // General-key scoring (ldgpu_general.hip): models with a gram length beyond
 // kMaxWideGram -- keys of any length in one table (GenSlot), compared byte for

@@ -2185,7 +2185,8 @@ __device__ __forceinline__ void group_load(const ScoreParams& p, int64_t s0, int
 // INVARIANT (cold_params): ScoreParams is the kernel's first and only explicit
 // argument, so it sits at offset 0 of the kernarg segment; the static_assert
 // after the kernel checks the signature.
-// IND (mode 1 only): the indirect launch of class mode's exact replay -- wave w
+// IND (modes 1 and 3): the indirect launch of class mode's exact replay, and of
+// count mode's documents that the trie kernel left (ldgpu_trie.hip) -- wave w
 // scores documents p.doc_idx[i], i = w, w + waves, ... < *p.n_docs_dev (count
 // written by the device), each in place from global memory, its label stored
 // to labels[doc_idx[i]]; workgroups with no document exit before staging.
@@ -2384,6 +2385,16 @@ hipError_t launch_w(const ScoreParams& p, int grid, hipStream_t stream) {
         }
     }
     if constexpr (MODE == 3) {
+        // (the documents the trie kernel left, ldgpu_trie.hip: a trie-eligible table has no wide key)
+        if (p.doc_idx) {
+            if constexpr (WIDE) {
+                return hipErrorInvalidValue;
+            } else {
+                hipLaunchKernelGGL((score_kernel<S, MODE, BL, false, false, true>), dim3(grid), dim3(kScoreWaves * 64),
+                                   lds, stream, p);
+                return hipGetLastError();
+            }
+        }
         if (pack) {
             hipLaunchKernelGGL((score_kernel<S, MODE, BL, true, WIDE>), dim3(grid), dim3(kScoreWaves * 64), lds,
                                stream, p);
@@ -2422,6 +2433,8 @@ hipError_t prepare_t(size_t lds, int* blocks) {
         if (e == hipSuccess) e = prepare_k<S, MODE, BL, false, true, true>(lds, &b3);
     }
     if constexpr (MODE == 3) {
+        int b3 = 0;  // (the indirect launch after the trie kernel: its LDS limit; it never sets the grid)
+        if (e == hipSuccess) e = prepare_k<S, MODE, BL, false, false, true>(lds, &b3);
         if (e == hipSuccess) e = prepare_k<S, MODE, BL, true>(lds, &b2);
         if (e == hipSuccess) *blocks = std::min(*blocks, b2);
         if (e == hipSuccess) e = prepare_k<S, MODE, BL, true, true>(lds, &b2);

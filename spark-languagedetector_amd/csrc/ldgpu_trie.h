@@ -1,0 +1,190 @@
+// ldgpu_trie.h -- the exact LDS trie of a small count-mode table (host only, no
+// HIP dependency: the model build includes it, and so does tools/trie_check.cpp).
+//
+// A table whose keys all have at most kTrieMaxLen bytes and name one language
+// each is laid out as a byte trie in one double array of 32-bit entries:
+//
+//   entry = check byte | language << 8 | child base << 16
+//
+//   language   the language of the counted key that ends at this node, or
+//              kTrieNoLang: none does (a pure prefix, or a key whose length the
+//              model's gramLengths do not list)
+//   child base BYTE offset of the node's row in the image (slot index * 4), so a
+//              step is one add: the child for byte c sits at base + 4 c
+//   check      the byte that leads to this node from its parent
+//
+// Every node with children has a DISTINCT base, so `slot - check = base` names
+// the parent exactly: a probe from another row lands on an entry whose check
+// differs from the probed byte.  The root's row is the image's first 256 slots,
+// exclusive and read unchecked (depth 1 is a direct table).  A node without
+// children, and every probe that misses, continues at the DEAD base: a base no
+// row uses, so whatever slot a dead walk reads mismatches for ever.  An empty
+// slot s carries a check c for which s - c is no used base (the dead base
+// counts as used), language kTrieNoLang and the dead base.
+//
+// A walk reads slots up to base + 255 for any text byte, so every base leaves
+// 256 slots to the end of the image.
+#pragma once
+
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+
+namespace ldgpu {
+
+constexpr int kTrieMaxLen = 4;
+constexpr uint32_t kTrieNoLang = 0xffu;
+constexpr uint32_t kTrieMaxLangs = 254;      // languages 0..253: the counter index is the entry's byte
+constexpr uint32_t kTrieMaxSlots = 16384;    // 64 KiB: a byte offset fits the entry's 16 bits
+
+struct TrieKey {
+    uint32_t bytes;  // the key's bytes little-endian (byte 0 first), zero above len
+    uint8_t len;     // 1..kTrieMaxLen
+    uint8_t lang;    // < kTrieMaxLangs; kTrieNoLang: a key that is not counted (it adds nothing)
+};
+
+struct TrieImage {
+    std::vector<uint32_t> words;  // the image, a multiple of 4 words
+    uint32_t dead = 0;            // the dead entry (language kTrieNoLang, the dead base)
+    uint32_t nodes = 0;           // trie nodes below the root
+    uint32_t rows = 0;            // nodes with children (the root included)
+    int max_len = 0;              // the longest counted key
+};
+
+constexpr uint32_t trie_entry(uint32_t check, uint32_t lang, uint32_t base_slot) {
+    return check | lang << 8 | (base_slot * 4u) << 16;
+}
+constexpr uint32_t trie_check(uint32_t e) { return e & 0xffu; }
+constexpr uint32_t trie_lang(uint32_t e) { return (e >> 8) & 0xffu; }
+constexpr uint32_t trie_base_slot(uint32_t e) { return e >> 18; }
+
+// the walk the kernel makes, for the host check: the entry after byte c from
+// entry e (root: the direct table); a miss gives the dead entry
+inline uint32_t trie_root(const TrieImage& t, uint8_t c) { return t.words[c]; }
+inline uint32_t trie_step(const TrieImage& t, uint32_t e, uint8_t c) {
+    const uint32_t n = t.words[trie_base_slot(e) + c];
+    return trie_check(n) == c ? n : t.dead;
+}
+
+// Builds the image of `keys` (distinct) within max_slots slots.  False: a key
+// out of the rule, two languages for one key, or no packing within max_slots.
+inline bool trie_build(const std::vector<TrieKey>& keys, uint32_t max_slots, TrieImage& out) {
+    struct Node {
+        uint32_t parent;
+        uint8_t byte, lang;
+        std::vector<uint32_t> kids;  // node indices
+        uint32_t base = 0;           // slot index of the row (nodes with kids)
+    };
+    max_slots = std::min(max_slots, kTrieMaxSlots);
+    if (max_slots < 512) return false;
+    std::vector<Node> nodes(1, Node{0, 0, (uint8_t)kTrieNoLang, {}, 0});
+    out = TrieImage{};
+    // keys in (bytes as a string) order: every row's children come out sorted
+    std::vector<TrieKey> ks;
+    for (const TrieKey& k : keys) {
+        if (k.len < 1 || k.len > kTrieMaxLen) return false;
+        if (k.lang == kTrieNoLang) continue;
+        if (k.lang >= kTrieMaxLangs) return false;
+        ks.push_back(k);
+    }
+    // (every key is a node of its own and every node takes a slot: more counted
+    // keys, or more nodes, than slots cannot pack -- found before the trie is built)
+    if (ks.size() > max_slots) return false;
+    for (const TrieKey& k : ks) {
+        if (nodes.size() > max_slots + 1) return false;
+        uint32_t at = 0;
+        for (int d = 0; d < k.len; ++d) {
+            const uint8_t c = (uint8_t)(k.bytes >> (8 * d));
+            uint32_t next = 0;
+            for (uint32_t kid : nodes[at].kids)
+                if (nodes[kid].byte == c) next = kid;
+            if (!next) {
+                next = (uint32_t)nodes.size();
+                nodes.push_back(Node{at, c, (uint8_t)kTrieNoLang, {}, 0});
+                nodes[at].kids.push_back(next);
+            }
+            at = next;
+        }
+        if (nodes[at].lang != kTrieNoLang && nodes[at].lang != k.lang) return false;
+        nodes[at].lang = k.lang;
+        out.max_len = std::max(out.max_len, (int)k.len);
+    }
+    out.nodes = (uint32_t)nodes.size() - 1;
+
+    // first-fit row displacement, largest rows first; the root's row is slots
+    // 0..255, exclusive.  A row may start below slot 256 (its base only has to
+    // keep its ENTRIES out of the root's row) but not past max_slots - 256.
+    std::vector<uint32_t> rows;
+    for (uint32_t i = 1; i < nodes.size(); ++i)
+        if (!nodes[i].kids.empty()) rows.push_back(i);
+    std::stable_sort(rows.begin(), rows.end(),
+                     [&](uint32_t a, uint32_t b) { return nodes[a].kids.size() > nodes[b].kids.size(); });
+    out.rows = (uint32_t)rows.size() + 1;
+    std::vector<uint8_t> taken(max_slots, 0), used_base(max_slots, 0);
+    std::vector<int32_t> owner(max_slots, -1);  // the node of an occupied slot
+    for (uint32_t s = 0; s < 256; ++s) taken[s] = 1;
+    for (uint32_t kid : nodes[0].kids) owner[nodes[kid].byte] = (int32_t)kid;
+    used_base[0] = 1;
+    const uint32_t last_base = max_slots - 256;
+    uint32_t first_free = 256;
+    for (uint32_t r : rows) {
+        Node& n = nodes[r];
+        uint8_t lo = 255;
+        for (uint32_t kid : n.kids) lo = std::min(lo, nodes[kid].byte);
+        while (first_free < max_slots && taken[first_free]) ++first_free;
+        bool placed = false;
+        // the row's lowest child on each free slot in turn
+        for (uint32_t s = first_free; s < max_slots && !placed; ++s) {
+            if (taken[s] || s < lo) continue;
+            const uint32_t base = s - lo;
+            if (base < 1 || base > last_base) continue;
+            if (used_base[base]) continue;
+            bool fits = true;
+            for (uint32_t kid : n.kids) fits &= !taken[base + nodes[kid].byte];
+            if (!fits) continue;
+            n.base = base;
+            used_base[base] = 1;
+            for (uint32_t kid : n.kids) {
+                taken[base + nodes[kid].byte] = 1;
+                owner[base + nodes[kid].byte] = (int32_t)kid;
+            }
+            placed = true;
+        }
+        if (!placed) return false;
+    }
+    // the dead base: the lowest one no row uses
+    uint32_t dead_base = 1;
+    while (dead_base <= last_base && used_base[dead_base]) ++dead_base;
+    if (dead_base > last_base) return false;
+    used_base[dead_base] = 1;
+    uint32_t top = 0;
+    for (uint32_t b = 0; b <= last_base; ++b)
+        if (used_base[b]) top = b;
+    const uint32_t n_slots = (top + 256 + 3) & ~3u;
+    if (n_slots > max_slots) return false;
+    out.dead = trie_entry(0, kTrieNoLang, dead_base);
+    out.words.assign(n_slots, 0u);
+    for (uint32_t s = 0; s < n_slots; ++s) {
+        if (owner[s] >= 0) {
+            const Node& n = nodes[(size_t)owner[s]];
+            out.words[s] = trie_entry(n.byte, n.lang, n.kids.empty() ? dead_base : n.base);
+            continue;
+        }
+        // an empty slot: a check byte that names no row
+        int c = -1;
+        for (int t = 0; t < 256 && c < 0; ++t)
+            if ((uint32_t)t > s || !used_base[s - (uint32_t)t]) c = t;
+        if (c < 0) return false;
+        out.words[s] = trie_entry((uint32_t)c, kTrieNoLang, dead_base);
+    }
+    return true;
+}
+
+// bytes of LDS the trie kernel needs per workgroup of `waves` waves: the image,
+// then per wave the language counters, the double-buffered staging and the
+// group's labels (one byte each: a language below kTrieMaxLangs, or 0xff = -1)
+constexpr uint32_t trie_lds_bytes(uint32_t image_words, int slices, int waves, uint32_t buf_words) {
+    return image_words * 4u + (uint32_t)waves * (64u * (uint32_t)slices * 4u + 2u * buf_words * 4u + 64u);
+}
+
+}  // namespace ldgpu

@@ -1,0 +1,326 @@
+// ldgpu_trie.hip -- SCORE count mode on an exact LDS trie (gfx950).
+//
+// A count-mode table whose keys all have at most kTrieMaxLen bytes and name one
+// language each, and whose byte trie packs into the LDS two workgroups per CU
+// leave (ldgpu_trie.h: layout and builder), is scored without Bloom filter,
+// candidate queue, verify or global-memory lookup: every window position walks
+// the trie, at most one LDS word per key length, and yields the hit and the
+// language of lengths 1..4 on the way.
+//
+// The outer structure is score_kernel's (ldgpu_score.hip): a persistent grid of
+// kScoreWaves waves per workgroup, one contiguous document range per wave,
+// groups of consecutive documents staged by double-buffered LDS-DMA, the
+// group's labels written in one coalesced store.  A staged document of
+// maxg..256 bytes is scored in the lane-run layout, lane i owning positions
+// 4 i .. 4 i + 3:
+//   run bytes  bytes 0..6 of the lane's run from three staged dwords
+//              (v_alignbyte by the wave-uniform base & 3), and their seven
+//              scaled offsets 4 * byte: each serves up to four walks
+//   depth 1    four entries of the direct table (the image's first 256 words)
+//   depth d    entry.base + offset[k + d - 1], one ds_read_b32 per position,
+//              the four of a depth back to back; a check byte that differs from
+//              the text byte replaces the entry by the dead entry
+//   counting   per depth one wave-level test "any lane holds a terminal", then
+//              at most four exec-masked LDS adds of mult[depth]
+//   tail       a window of N bytes at position p = 4 lane + k counts only if
+//              p + N <= len, which depends on k + N alone: seven lane masks
+//              in SGPRs, kept from one document to the next and rebuilt (one
+//              v_cmp each) only when the length changes, and-ed into the
+//              exec mask of a terminal's add -- the walks themselves run past
+//              the document's end unchecked (the bytes there are the next
+//              document's, or the buffer's padding)
+//   label      the count argmax (first maximum), as score_kernel's
+// Every other document -- shorter than maxg (partial windows), longer than 256
+// bytes, or in a group the staging buffer does not hold -- gets label -1 and
+// is appended to a list (p.left, its length counted in *p.n_left); an indirect
+// launch of the mode-3 score_kernel then scores the listed documents in place
+// and leaves at once when there is none (score_launch, ldgpu_api.hip).
+#include "ldgpu_internal.h"
+#include "ldgpu_wave.h"
+
+namespace ldgpu {
+namespace {
+
+typedef __attribute__((address_space(3))) uint32_t lds_u32;
+typedef __attribute__((address_space(3))) uint8_t lds_u8;
+
+__device__ __forceinline__ int64_t rdlane_i64(int64_t v, int l) {
+    return (int64_t)((uint64_t)rdlane((uint32_t)v, l) | ((uint64_t)rdlane((uint32_t)((uint64_t)v >> 32), l) << 32));
+}
+
+// lane id recomputed in place (never spilled: see score_kernel's fresh_lane)
+__device__ __forceinline__ uint32_t fresh_lane() {
+    uint32_t l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+}
+
+// LDS-DMA of a group's bytes [s0, s0 + kBufBytes) into dst (lane i's 16 B land
+// at dst + 16 i), range-checked: bytes past n_bytes read as 0, never fault
+__device__ __forceinline__ void group_dma(const TrieParams& p, int64_t s0, uint32_t* dst) {
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(p.bytes + s0));
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uintptr_t)(p.bytes + s0) >> 32));
+    const int64_t left = ((p.n_bytes + 3) & ~(int64_t)3) - s0;
+    const uint32_t nrec =
+        __builtin_amdgcn_readfirstlane((uint32_t)(left < 0 ? 0 : (left > 0x7ffffff0 ? 0x7ffffff0 : left)));
+    void* base = (void*)(((uint64_t)hi << 32) | lo);
+    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(base, (short)0, (int)nrec, 0x00020000);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)dst, 16, 16 * fresh_lane(), 0,
+                                             0, 0);
+}
+
+// the label of the document counted in cnt (first maximum of the counts: the
+// fold of c adds of the table's one value is strictly monotone in c); clears
+// the counters -- score_kernel's count_argmax
+template <int S>
+__device__ __forceinline__ int count_argmax(const TrieParams& p, uint32_t* cnt, int lane) {
+    uint32_t best = 0;
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+        const int l = 64 * s + lane;
+        if (l < p.L) {
+            const uint32_t c = cnt[l];
+            cnt[l] = 0;
+            const uint32_t k = p.count_sign > 0 ? c : (p.count_sign < 0 ? 0xffffffu - c : 0u);
+            best = max(best, (k << 8) | (uint32_t)(255 - l));
+        }
+    }
+    return 255 - (int)(wave_max_u32(best) & 255u);
+}
+
+// a staged label byte as the label: a language 0..253 as it stands, 0xff = -1
+__device__ __forceinline__ int32_t label_of(uint8_t v) { return v == 0xffu ? -1 : (int32_t)v; }
+
+__device__ __forceinline__ uint32_t lds_word(uint32_t byte_addr) { return *(const lds_u32*)(size_t)byte_addr; }
+
+// The tail cut, kept from one document to the next: lane mask c - 1 = a window
+// that ends c bytes after the lane's first position ends inside a document of
+// `len` bytes.  Rebuilt only when the length changes (a wave-uniform compare).
+struct TailCut {
+    uint64_t in[7];
+    int32_t len;  // the length the masks were built for (-1: none yet)
+};
+
+template <int MAXD>
+__device__ __forceinline__ void tail_cut(TailCut& cut, int32_t len, int lane) {
+    if (cut.len == len) return;
+    const int32_t left = len - 4 * lane;
+#pragma unroll
+    for (int c = 1; c <= 3 + MAXD; ++c) cut.in[c - 1] = __builtin_amdgcn_ballot_w64(left >= c);
+    cut.len = len;
+}
+
+// the terminals of depth D among the lane's four entries, counted
+template <int D>
+__device__ __forceinline__ void count_depth(const TrieParams& p, uint32_t* cnt, const uint32_t (&e)[4],
+                                            const TailCut& cut, uint32_t inc) {
+    // one wave-level test: a byte of 0xff in all four entries = no terminal
+    // (a terminal past the document's end only keeps the wave on this path)
+    const uint32_t all = e[0] & e[1] & e[2] & e[3];
+    if (!__builtin_amdgcn_ballot_w64(__builtin_amdgcn_ubfe(all, 8, 8) != kTrieNoLang)) return;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t lang = __builtin_amdgcn_ubfe(e[k], 8, 8);
+        const bool in = __builtin_amdgcn_inverse_ballot_w64(cut.in[k + D - 1]);
+        if (lang != kTrieNoLang && in)
+            __hip_atomic_fetch_add(&cnt[lang], inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+}
+
+// One staged document of maxg..256 bytes at byte `base` of the wave's buffer.
+template <int S, int MAXD>
+__device__ __forceinline__ int trie_doc(const TrieParams& p, uint32_t dead, uint32_t* cnt,
+                                        const uint32_t* buf, uint32_t base, int32_t len, int lane, TailCut& cut) {
+    // run bytes 0..6 of the lane's four positions.  Bound: lane 63 reads dwords
+    // (base >> 2) + 63 .. + 65, within what score_kernel's lane runs read.
+    const uint32_t sh = base & 3u;  // wave-uniform
+    const uint32_t* w = buf + (base >> 2) + lane;
+    const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
+    const uint32_t r0 = __builtin_amdgcn_alignbyte(w1, w0, sh);  // run bytes 0..3
+    const uint32_t r1 = __builtin_amdgcn_alignbyte(w2, w1, sh);  // 4..7
+    uint32_t b[7], off[7];
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+        b[j] = ((j < 4 ? r0 : r1) >> (8 * (j & 3))) & 0xffu;
+        off[j] = b[j] << 2;
+    }
+    tail_cut<MAXD>(cut, len, lane);
+    uint32_t e[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) e[k] = lds_word(off[k]);  // (the direct table at LDS address 0: no check)
+#pragma unroll
+    for (int d = 1; d <= MAXD; ++d) {
+        uint32_t n[4];
+        if (d < MAXD) {
+            // the next depth's four reads, issued before this depth is counted
+#pragma unroll
+            for (int k = 0; k < 4; ++k) n[k] = lds_word((e[k] >> 16) + off[k + d]);
+        }
+        const uint32_t inc = p.mult[d];
+        if (inc) {
+            if (d == 1) count_depth<1>(p, cnt, e, cut, inc);
+            if (d == 2) count_depth<2>(p, cnt, e, cut, inc);
+            if (d == 3) count_depth<3>(p, cnt, e, cut, inc);
+            if (d == 4) count_depth<4>(p, cnt, e, cut, inc);
+        }
+        if (d < MAXD) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) e[k] = (n[k] & 0xffu) == b[k + d] ? n[k] : dead;
+        }
+    }
+    return count_argmax<S>(p, cnt, lane);
+}
+
+template <int S, int MAXD>
+__global__ __launch_bounds__(kScoreWaves * 64, kScoreMinWgPerCu * kScoreWaves / 4) void trie_kernel(const TrieParams p) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // The image's bases are LDS byte addresses as they stand: the image starts
+    // the dynamic region, which starts at LDS address 0 because this file has
+    // no static __shared__ variable (the static size is a link-time constant;
+    // were it ever not 0, the kernel would write no label and every test fail).
+    if (__builtin_amdgcn_groupstaticsize() != 0) return;
+    {
+        const uint4* src = reinterpret_cast<const uint4*>(p.image);
+        uint4* dst = reinterpret_cast<uint4*>(lds);
+        for (uint32_t i = tid; i < (p.image_words >> 2); i += blockDim.x) dst[i] = src[i];
+    }
+    const uint32_t dead = p.dead;
+    __syncthreads();
+    uint32_t* const cnt = lds + p.image_words + wave * (64 * S);
+    uint32_t* const buf0 = lds + p.image_words + kScoreWaves * (64 * S) + wave * 2 * kBufWords;
+    uint32_t* const buf1 = buf0 + kBufWords;
+    uint8_t* const labels =
+        reinterpret_cast<uint8_t*>(lds + p.image_words + kScoreWaves * (64 * S + 2 * kBufWords)) + wave * 64;
+#pragma unroll
+    for (int s = 0; s < S; ++s) cnt[64 * s + lane] = 0;
+    __builtin_amdgcn_wave_barrier();
+
+    // this wave's contiguous range of documents, walked in groups of p.group
+    const int64_t nwaves = (int64_t)gridDim.x * kScoreWaves;
+    const int64_t wg = (int64_t)blockIdx.x * kScoreWaves + wave;
+    const int64_t dbeg = (int64_t)((__int128)p.n_docs * wg / nwaves);
+    const int64_t dend = (int64_t)((__int128)p.n_docs * (wg + 1) / nwaves);
+    if (dbeg >= dend) return;
+    const int G = p.group;
+
+    // lane i <= G holds offsets[g0 + i] of the current group (clamped to dend)
+    int64_t g0 = dbeg;
+    int64_t offv = p.offsets[min(g0 + (int64_t)min(lane, G), dend)];
+    group_dma(p, rdlane_i64(offv, 0) & ~(int64_t)15, buf0);
+    bool par = false;
+    int64_t prev_g0 = 0;
+    int prev_cnt = 0;
+    TailCut cut;
+    cut.len = -1;
+
+    while (g0 < dend) {
+        // this group's bytes (DMA issued one group ago) have landed, and the
+        // previous group's label store has drained
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_wave_barrier();
+        // as many consecutive whole documents as the staging buffer holds from
+        // s0 (at least one: the lanes that fit are a prefix)
+        const int64_t s0 = rdlane_i64(offv, 0) & ~(int64_t)15;
+        const int lim = (int)min((int64_t)G, dend - g0);
+        const int fl = (int)fresh_lane();
+        const int cntd = max(1, (int)__popcll(__ballot(fl >= 1 && fl <= lim && offv - s0 <= (int64_t)kBufBytes)));
+        const int64_t g1 = g0 + cntd;
+        const int64_t send = rdlane_i64(offv, cntd);
+        const bool staged = send - s0 <= kBufBytes;
+        uint32_t* const cur = par ? buf1 : buf0;
+        // bytes and offsets of the next group (hidden behind this group's work)
+        if (g1 < dend) group_dma(p, send & ~(int64_t)15, par ? buf0 : buf1);
+        const int64_t n1 = min(g1 + (int64_t)G, dend);
+        const int64_t offn = p.offsets[min(g1 + (int64_t)min((int)fresh_lane(), G), n1)];
+        // the previous group's labels: one coalesced store (0xff = -1)
+        {
+            const uint32_t l = fresh_lane();
+            if ((int)l < prev_cnt) p.labels[prev_g0 + l] = label_of(labels[l]);
+        }
+        __builtin_amdgcn_wave_barrier();
+        for (int i = 0; i < cntd; ++i) {
+            // 32-bit geometry (a staged group: b - s0 and len lie in [0, kBufBytes])
+            const uint32_t blo = rdlane((uint32_t)offv, i);
+            const int32_t len = (int32_t)(rdlane((uint32_t)offv, i + 1) - blo);
+            const uint32_t base = blo - (uint32_t)s0;
+            int lab;
+            if (staged && len >= p.maxg && len <= 256) {
+                lab = trie_doc<S, MAXD>(p, dead, cnt, cur, base, len, lane, cut);
+            } else {
+                // left to the indirect launch of score_kernel
+                lab = 0xff;
+                if (lane == 0) p.left[atomicAdd(p.n_left, 1ull)] = g0 + i;
+            }
+            if (lane == 0) labels[i] = (uint8_t)lab;
+        }
+        __builtin_amdgcn_wave_barrier();
+        prev_g0 = g0;
+        prev_cnt = cntd;
+        offv = offn;
+        g0 = g1;
+        par = !par;
+    }
+    if (lane < prev_cnt) p.labels[prev_g0 + lane] = label_of(labels[lane]);
+}
+
+template <int S, int MAXD>
+hipError_t launch_k(const TrieParams& p, int grid, size_t lds, hipStream_t stream) {
+    hipLaunchKernelGGL((trie_kernel<S, MAXD>), dim3(grid), dim3(kScoreWaves * 64), lds, stream, p);
+    return hipGetLastError();
+}
+template <int S>
+hipError_t launch_s(const TrieParams& p, int max_len, int grid, size_t lds, hipStream_t stream) {
+    switch (max_len) {
+        case 1: return launch_k<S, 1>(p, grid, lds, stream);
+        case 2: return launch_k<S, 2>(p, grid, lds, stream);
+        case 3: return launch_k<S, 3>(p, grid, lds, stream);
+        case 4: return launch_k<S, 4>(p, grid, lds, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+template <int S, int MAXD>
+hipError_t prepare_k(size_t lds, int* blocks) {
+    const void* f = reinterpret_cast<const void*>(&trie_kernel<S, MAXD>);
+    hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, f, kScoreWaves * 64, lds);
+}
+template <int S>
+hipError_t prepare_s(int max_len, size_t lds, int* blocks) {
+    switch (max_len) {
+        case 1: return prepare_k<S, 1>(lds, blocks);
+        case 2: return prepare_k<S, 2>(lds, blocks);
+        case 3: return prepare_k<S, 3>(lds, blocks);
+        case 4: return prepare_k<S, 4>(lds, blocks);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_trie(const TrieParams& p, int slices, int max_len, int grid, hipStream_t stream) {
+    const size_t lds = trie_lds_bytes(p.image_words, slices, kScoreWaves, kBufWords);
+    switch (slices) {
+        case 1: return launch_s<1>(p, max_len, grid, lds, stream);
+        case 2: return launch_s<2>(p, max_len, grid, lds, stream);
+        case 3: return launch_s<3>(p, max_len, grid, lds, stream);
+        case 4: return launch_s<4>(p, max_len, grid, lds, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t trie_prepare(int slices, int max_len, size_t lds_bytes, int* blocks_per_cu) {
+    switch (slices) {
+        case 1: return prepare_s<1>(max_len, lds_bytes, blocks_per_cu);
+        case 2: return prepare_s<2>(max_len, lds_bytes, blocks_per_cu);
+        case 3: return prepare_s<3>(max_len, lds_bytes, blocks_per_cu);
+        case 4: return prepare_s<4>(max_len, lds_bytes, blocks_per_cu);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace ldgpu

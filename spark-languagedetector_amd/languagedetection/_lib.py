@@ -37,7 +37,7 @@ MAX_TOPK = 16  # LDGPU_MAX_TOPK
 LAYOUT_FLAGS = {"lds_bloom": 0x01, "keyed_bloom": 0x02, "keyed_bloom_lines": 0x04, "buckets": 0x08,
                 "wide_keys": 0x10, "direct": 0x20, "packs": 0x40, "lang_blocks": 0x80,
                 "general_keys": 0x100, "keyed_bloom_chunks": 0x200, "classes": 0x400,
-                "narrow_slots": 0x800}
+                "narrow_slots": 0x800, "trie": 0x1000}
 
 _p = ctypes.c_void_p
 _pp = ctypes.POINTER(ctypes.c_void_p)
@@ -210,8 +210,8 @@ def device_count() -> int:
 # the sources the library is built from, in the Makefile's PROV order
 _PROV = ["csrc/ldgpu_api.hip", "csrc/ldgpu_score.hip", "csrc/ldgpu_fit.hip", "csrc/ldgpu_general.hip",
          "csrc/ldgpu_long.hip", "csrc/ldgpu_replay.hip", "csrc/ldgpu_pre.hip", "csrc/ldgpu_topk.hip",
-         "csrc/ldgpu_spans.hip", "csrc/ldgpu_segments.hip", "csrc/ldgpu_common.h", "csrc/ldgpu_internal.h",
-         "csrc/ldgpu_wave.h", "csrc/ldgpu_fit.h", "../include/ldgpu.h"]
+         "csrc/ldgpu_spans.hip", "csrc/ldgpu_segments.hip", "csrc/ldgpu_trie.hip", "csrc/ldgpu_common.h",
+         "csrc/ldgpu_internal.h", "csrc/ldgpu_wave.h", "csrc/ldgpu_trie.h", "csrc/ldgpu_fit.h", "../include/ldgpu.h"]
 
 
 def tree_source_hash() -> str:
