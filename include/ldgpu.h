@@ -483,6 +483,77 @@ int ldgpu_preprocess_device(ldgpu_casemap* map, const uint16_t* d_units, const i
 int ldgpu_preprocess(ldgpu_casemap* map, const uint16_t* units, const int64_t* offsets, int64_t n_docs,
                      const uint8_t* locale, int32_t flags, void* out, int64_t* out_offsets, uint8_t* host);
 
+/* ---------------------------------------------------------------- UTF-8 */
+/* FIT counts a text's UTF-8 bytes, SCORE scans the low byte of every UTF-16
+ * code unit (LanguageDetector.scala:37, LanguageDetectorModel.scala:161).  These
+ * calls take the UTF-8 a caller stores and produce the other side's input on
+ * the device: UTF-16 units (ldgpu_preprocess_device's input) or, with
+ * LDGPU_PRE_LOW_BYTES, the SCORE encoding (ldgpu_score_device's input).
+ *
+ * A document is well-formed iff its bytes are a concatenation of the sequences
+ * of Unicode Table 3-7:
+ *   00..7F
+ *   C2..DF 80..BF
+ *   E0     A0..BF 80..BF
+ *   E1..EC 80..BF 80..BF
+ *   ED     80..9F 80..BF
+ *   EE..EF 80..BF 80..BF
+ *   F0     90..BF 80..BF 80..BF
+ *   F1..F3 80..BF 80..BF 80..BF
+ *   F4     80..8F 80..BF 80..BF
+ * Everything else is ill-formed: C0, C1 and F5..FF anywhere, a continuation
+ * byte without a lead, an overlong form, an encoded surrogate (ED A0..BF), a
+ * value beyond U+10FFFF, and a sequence cut off by the end of its document (a
+ * sequence never borrows bytes from the next document).  These are exactly the
+ * byte strings CPython's bytes.decode("utf-8") accepts.  00 is an ordinary
+ * character (C0 80 is ill-formed); EF BB BF is U+FEFF and stays in the output.
+ *
+ * Units of a well-formed document: a code point cp < 0x10000 gives the unit
+ * cp; a larger one, v = cp - 0x10000, the two units 0xD800 + (v >> 10) and
+ * 0xDC00 + (v & 0x3FF) -- what new String(bytes, UTF_8) and
+ * UTF8String.toString give, so an output index is a Java String index.  With
+ * LDGPU_PRE_LOW_BYTES the output is (uint8_t)unit per unit.
+ *
+ * An ill-formed document is not decoded: host[d] = 1 and its output is empty
+ * (out_offsets[d + 1] == out_offsets[d]).  Which replacement characters a
+ * decoder would insert stays the caller's business, as the context-dependent
+ * documents of the preprocessors do. */
+#define LDGPU_UTF8_STEP_BYTES 256  /* bytes of a document one wave takes per step (tests place sequences across it) */
+
+/* Device buffers, asynchronous on `stream` (NULL: the default stream).  flags:
+ * 0 or LDGPU_PRE_LOW_BYTES, anything else is LDGPU_EINVAL.  d_utf8 must be
+ * 4-byte aligned, and the bytes up to d_offsets[n_docs] rounded up to 4 must
+ * be readable (the rule of ldgpu_score_device's d_bytes); nothing beyond them
+ * and nothing before d_offsets[0] rounded down to 4 is read.  d_out holds
+ * d_offsets[n_docs] - d_offsets[0] units (bytes with the flag): a document
+ * never gives more units than it has bytes.  d_out_offsets [n_docs + 1]
+ * receives the output's offsets (from 0); d_host [n_docs].  Offsets are
+ * trusted; n_docs < 2^31 - 1 (the scan), beyond is LDGPU_EUNSUPPORTED. */
+int ldgpu_utf8_decode_device(ldgpu_ctx* ctx, const uint8_t* d_utf8, const int64_t* d_offsets, int64_t n_docs,
+                             int32_t flags, void* d_out, int64_t* d_out_offsets, uint8_t* d_host, void* stream);
+/* The same over host buffers (copied in and out; returns when done). */
+int ldgpu_utf8_decode(ldgpu_ctx* ctx, const uint8_t* utf8, const int64_t* offsets, int64_t n_docs,
+                      int32_t flags, void* out, int64_t* out_offsets, uint8_t* host);
+
+/* ldgpu_score on UTF-8 documents.  A well-formed document's label and score
+ * row are bit for bit those ldgpu_score gives for its SCORE encoding, on every
+ * model layout.  An ill-formed document gets label -1 and the score row of an
+ * empty document: the caller decodes it under its own replacement rule and
+ * scores it with ldgpu_score.  Only the UTF-8 bytes cross to the device; each
+ * chunk is decoded there and scored from the decoded bytes.  Argument checks,
+ * LDGPU_EROWLEN, thread safety and the pipeline over pinned / pageable buffers
+ * are those of ldgpu_score; the 2^28 limit applies to a document's UTF-8
+ * length. */
+int ldgpu_score_utf8(ldgpu_model* model, const uint8_t* utf8, const int64_t* offsets, int64_t n_docs,
+                     int32_t* out_labels, double* out_scores);
+/* Device-resident variant, asynchronous on `stream` under the rules of
+ * ldgpu_score_device (d_utf8 4-byte aligned, n_bytes >= d_offsets[n_docs]).
+ * The documents are decoded into stream-ordered scratch (n_bytes of decoded
+ * bytes, the offsets and flags of a chunk of at most 2^24 documents) and scored
+ * from there: nothing is read back. */
+int ldgpu_score_utf8_device(ldgpu_model* model, const uint8_t* d_utf8, int64_t n_bytes, const int64_t* d_offsets,
+                            int64_t n_docs, int32_t* d_labels, double* d_scores, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

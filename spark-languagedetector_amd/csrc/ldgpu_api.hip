@@ -253,6 +253,9 @@ struct ScoreStage {
     // top-k calls (ldgpu_score_topk): the chunk's [nd][k] labels and scores
     // (`labels` and `scores` are then the scratch they are selected from)
     DevBuf top_labels, top_scores;
+    // UTF-8 calls (ldgpu_score_utf8): the chunk's decoded SCORE bytes, their
+    // offsets and the ill-formed flags (`bytes` and `offsets` hold the UTF-8)
+    DevBuf dec, dec_offsets, dec_host;
     int64_t d0 = 0, nd = 0;  // the chunk in flight: its first item and their number
     bool busy = false;
 };
@@ -353,7 +356,9 @@ namespace {
 void pipe_destroy(ScorePipe* pp) {
     for (auto& st : pp->stage) {
         if (st.stream) (void)hipStreamSynchronize(st.stream);
-        for (DevBuf* b : {&st.bytes, &st.offsets, &st.labels, &st.scores, &st.top_labels, &st.top_scores}) b->release();
+        for (DevBuf* b : {&st.bytes, &st.offsets, &st.labels, &st.scores, &st.top_labels, &st.top_scores, &st.dec,
+                          &st.dec_offsets, &st.dec_host})
+            b->release();
         for (HostBuf* b : {&st.h_bytes, &st.h_offsets, &st.h_labels, &st.h_scores}) b->release();
         if (st.done) (void)hipEventDestroy(st.done);
         if (st.stream) (void)hipStreamDestroy(st.stream);
@@ -543,10 +548,13 @@ extern "C" int ldgpu_preprocess_device(ldgpu_casemap* m, const uint16_t* d_units
     p.host = d_host;
     size_t scan_bytes = 0;
     HIP_TRY(launch_preprocess(p, nullptr, nullptr, nullptr, &scan_bytes, m->ctx->cus, st));
-    int64_t* len_tmp = nullptr;
-    HIP_TRY(hipMallocAsync((void**)&len_tmp, sizeof(int64_t) * (size_t)(n_docs + 1) + scan_bytes + 16, st));
-    const hipError_t e = launch_preprocess(p, len_tmp, d_out_offsets, len_tmp + n_docs + 1, &scan_bytes, m->ctx->cus, st);
-    (void)hipFreeAsync(len_tmp, st);
+    // the lengths, then the scan's scratch on a 256-byte boundary of the block
+    // (the scan loads 16-byte (value, flag) pairs from it whole)
+    const size_t len_bytes = (sizeof(int64_t) * (size_t)(n_docs + 1) + 255) & ~(size_t)255;
+    char* tmp = nullptr;
+    HIP_TRY(hipMallocAsync((void**)&tmp, len_bytes + scan_bytes, st));
+    const hipError_t e = launch_preprocess(p, (int64_t*)tmp, d_out_offsets, tmp + len_bytes, &scan_bytes, m->ctx->cus, st);
+    (void)hipFreeAsync(tmp, st);
     HIP_TRY(e);
     return ok();
 }
@@ -585,6 +593,94 @@ extern "C" int ldgpu_preprocess(ldgpu_casemap* m, const uint16_t* units, const i
         if (e == hipSuccess)
             rc = ldgpu_preprocess_device(m, d_units, d_off, n_docs, locale ? d_loc : nullptr, flags, d_out, d_ooff,
                                          d_host, st);
+        if (e == hipSuccess && !rc) e = hipMemcpyAsync(out_offsets, d_ooff, a_off, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && !rc && n_docs) e = hipMemcpyAsync(host, d_host, (size_t)n_docs, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && !rc) e = hipStreamSynchronize(st);
+        if (e == hipSuccess && !rc && out_offsets[n_docs] > 0)
+            e = hipMemcpy(out, d_out, (size_t)out_offsets[n_docs] * ob, hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(d);
+    if (rc) return rc;
+    HIP_TRY(e);
+    return ok();
+}
+
+// -------------------------------------------------------------------- UTF-8
+// UTF-8 documents to UTF-16 units or the SCORE encoding (ldgpu_utf8.hip;
+// include/ldgpu.h UTF-8).
+namespace {
+// the three passes on st, their scratch stream-ordered; arguments checked by
+// the callers
+int utf8_decode_launch(int cus, const uint8_t* d_utf8, const int64_t* d_offsets, int64_t n_docs, int32_t flags,
+                       void* d_out, int64_t* d_out_offsets, uint8_t* d_host, hipStream_t st) {
+    Utf8Params p{};
+    p.utf8 = d_utf8;
+    p.offsets = d_offsets;
+    p.n_docs = n_docs;
+    p.flags = flags;
+    p.out = d_out;
+    p.host = d_host;
+    size_t scan_bytes = 0;
+    HIP_TRY(launch_utf8_decode(p, nullptr, nullptr, nullptr, &scan_bytes, cus, st));
+    // the lengths, then the scan's scratch on a 256-byte boundary of the block:
+    // the scan keeps 16-byte (value, flag) pairs there and loads them whole
+    const size_t len_bytes = (sizeof(int64_t) * (size_t)(n_docs + 1) + 255) & ~(size_t)255;
+    char* tmp = nullptr;
+    HIP_TRY(hipMallocAsync((void**)&tmp, len_bytes + scan_bytes, st));
+    const hipError_t e = launch_utf8_decode(p, (int64_t*)tmp, d_out_offsets, tmp + len_bytes, &scan_bytes, cus, st);
+    (void)hipFreeAsync(tmp, st);
+    HIP_TRY(e);
+    return LDGPU_OK;
+}
+}  // namespace
+
+extern "C" int ldgpu_utf8_decode_device(ldgpu_ctx* ctx, const uint8_t* d_utf8, const int64_t* d_offsets,
+                                        int64_t n_docs, int32_t flags, void* d_out, int64_t* d_out_offsets,
+                                        uint8_t* d_host, void* stream) {
+    if (!ctx) return fail(LDGPU_EINVAL, "ctx is NULL");
+    if (n_docs < 0) return fail(LDGPU_EINVAL, "n_docs < 0");
+    if (flags & ~LDGPU_PRE_LOW_BYTES) return fail(LDGPU_EINVAL, "unknown utf8 decode flags 0x%x", flags);
+    if (!d_out_offsets || (n_docs > 0 && (!d_offsets || !d_host || !d_out)))
+        return fail(LDGPU_EINVAL, "device pointer is NULL");
+    if (((uintptr_t)d_utf8 & 3) != 0) return fail(LDGPU_EINVAL, "d_utf8 must be 4-byte aligned");
+    if (n_docs >= (int64_t)std::numeric_limits<int>::max())
+        return fail(LDGPU_EUNSUPPORTED, "%lld documents in one call (the scan takes < 2^31)", (long long)n_docs);
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = utf8_decode_launch(ctx->cus, d_utf8, d_offsets, n_docs, flags, d_out, d_out_offsets, d_host,
+                                    (hipStream_t)stream))
+        return rc;
+    return ok();
+}
+
+extern "C" int ldgpu_utf8_decode(ldgpu_ctx* ctx, const uint8_t* utf8, const int64_t* offsets, int64_t n_docs,
+                                 int32_t flags, void* out, int64_t* out_offsets, uint8_t* host) {
+    if (!ctx) return fail(LDGPU_EINVAL, "ctx is NULL");
+    if (int rc = check_offsets(offsets, n_docs)) return rc;
+    if (flags & ~LDGPU_PRE_LOW_BYTES) return fail(LDGPU_EINVAL, "unknown utf8 decode flags 0x%x", flags);
+    if (!out_offsets || (n_docs > 0 && (!host || !out))) return fail(LDGPU_EINVAL, "output pointer is NULL");
+    const int64_t b0 = n_docs > 0 ? offsets[0] : 0, nb = n_docs > 0 ? offsets[n_docs] - b0 : 0;
+    if (nb > 0 && !utf8) return fail(LDGPU_EINVAL, "utf8 is NULL");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t ob = (flags & LDGPU_PRE_LOW_BYTES) ? 1 : 2;
+    std::vector<int64_t> off0((size_t)n_docs + 1);
+    for (int64_t i = 0; i <= n_docs; ++i) off0[(size_t)i] = n_docs > 0 ? offsets[i] - b0 : 0;
+    // one device block: bytes, offsets (in, out), flags, output
+    const size_t a_in = ((size_t)nb + 15) & ~(size_t)15, a_off = sizeof(int64_t) * ((size_t)n_docs + 1);
+    const size_t a_small = ((size_t)n_docs + 15) & ~(size_t)15, a_out = ((size_t)nb * ob + 15) & ~(size_t)15;
+    uint8_t* d = nullptr;
+    HIP_TRY(hipMalloc((void**)&d, a_in + 2 * a_off + a_small + a_out + 16));
+    int64_t* d_off = (int64_t*)(d + a_in);
+    int64_t* d_ooff = (int64_t*)(d + a_in + a_off);
+    uint8_t* d_host = d + a_in + 2 * a_off;
+    void* d_out = d_host + a_small;
+    hipStream_t st = ctx->stream;
+    int rc = LDGPU_OK;
+    hipError_t e = hipSuccess;
+    {
+        std::lock_guard<std::mutex> lock(ctx->mu);  // the context's stream
+        if (nb) e = hipMemcpyAsync(d, utf8 + b0, (size_t)nb, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_off, off0.data(), a_off, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) rc = ldgpu_utf8_decode_device(ctx, d, d_off, n_docs, flags, d_out, d_ooff, d_host, st);
         if (e == hipSuccess && !rc) e = hipMemcpyAsync(out_offsets, d_ooff, a_off, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess && !rc && n_docs) e = hipMemcpyAsync(host, d_host, (size_t)n_docs, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess && !rc) e = hipStreamSynchronize(st);
@@ -2453,6 +2549,87 @@ extern "C" int ldgpu_score_topk(ldgpu_model* m, const uint8_t* bytes, const int6
     return with_pipe(m, [&](ScorePipe* pp) {
         return run_score_pipe(m, pp, call, doc_chunks(offsets, n_docs, max_docs), launch);
     });
+}
+
+// ------------------------------------------------------------- SCORE: UTF-8
+// UTF-8 documents scored without a host transcode (include/ldgpu.h): decoded
+// to the SCORE encoding on the device (ldgpu_utf8.hip), the decoded corpus fed
+// to score_launch -- every model kind's own path -- and the label of an
+// ill-formed document (decoded to nothing, so its score row is the empty
+// document's) set to -1 afterwards.
+namespace {
+// the decoded bytes number at most the UTF-8 bytes (n_bytes, which score_launch
+// then takes as the readable size of d_dec: the scratch holds that and slack)
+int score_utf8_launch(ldgpu_model* m, const uint8_t* d_utf8, int64_t n_bytes, const int64_t* d_offsets,
+                      int64_t n_docs, uint8_t* d_dec, int64_t* d_dec_off, uint8_t* d_host, int32_t* d_labels,
+                      double* d_scores, int32_t* d_err, hipStream_t st) {
+    if (int rc = utf8_decode_launch(m->ctx->cus, d_utf8, d_offsets, n_docs, LDGPU_PRE_LOW_BYTES, d_dec, d_dec_off,
+                                    d_host, st))
+        return rc;
+    if (int rc = score_launch(m, d_dec, n_bytes, d_dec_off, n_docs, d_labels, d_scores, d_err, st)) return rc;
+    HIP_TRY(launch_utf8_labels(d_host, n_docs, d_labels, m->ctx->cus, st));
+    return LDGPU_OK;
+}
+
+// documents per chunk of the device form: bounds the offsets / flags scratch
+// and keeps the scan below 2^31 items
+int64_t utf8_chunk_docs() {
+    // (tests: chunks of a few documents)
+    if (const char* c = diag_env("LDGPU_UTF8_CHUNK_DOCS")) return std::max<int64_t>(1, atoll(c));
+    return 1ll << 24;
+}
+}  // namespace
+
+extern "C" int ldgpu_score_utf8(ldgpu_model* m, const uint8_t* utf8, const int64_t* offsets, int64_t n_docs,
+                                int32_t* out_labels, double* out_scores) {
+    if (int rc = check_host_call(m, utf8, offsets, n_docs, out_labels, "out_labels", true, no_own_checks)) return rc;
+    if (n_docs == 0) return ok();
+    const ScoreCall call{utf8, offsets, n_docs, nullptr, n_docs,
+                         {{&ScoreStage::labels, &ScoreStage::h_labels, out_labels, sizeof(int32_t)},
+                          {&ScoreStage::scores, &ScoreStage::h_scores, out_scores, sizeof(double) * m->L}}};
+    auto launch = [&](ScoreStage& st, const PipeChunk& ch, int32_t* d_err) -> int {
+        const int64_t nd = ch.i1 - ch.i0, nb = ch.hi - ch.lo;
+        HIP_TRY(st.dec.ensure((size_t)nb + 16));
+        HIP_TRY(st.dec_offsets.ensure(sizeof(int64_t) * (size_t)(nd + 1)));
+        HIP_TRY(st.dec_host.ensure((size_t)nd));
+        return score_utf8_launch(m, (const uint8_t*)st.bytes.p, nb, (const int64_t*)st.offsets.p, nd,
+                                 (uint8_t*)st.dec.p, (int64_t*)st.dec_offsets.p, (uint8_t*)st.dec_host.p,
+                                 (int32_t*)st.labels.p, out_scores ? (double*)st.scores.p : nullptr, d_err, st.stream);
+    };
+    return with_pipe(m, [&](ScorePipe* pp) {
+        return run_score_pipe(m, pp, call, doc_chunks(offsets, n_docs, score_chunk_docs()), launch);
+    });
+}
+
+// Chunks of documents (sub-ranges of d_offsets, absolute into d_utf8: nothing
+// is read back) decoded into stream-ordered scratch -- n_bytes of decoded
+// bytes, which every chunk reuses in stream order, and a chunk's offsets and
+// flags -- and scored from there.
+extern "C" int ldgpu_score_utf8_device(ldgpu_model* m, const uint8_t* d_utf8, int64_t n_bytes,
+                                       const int64_t* d_offsets, int64_t n_docs, int32_t* d_labels, double* d_scores,
+                                       void* stream) {
+    const bool null_ptr = n_docs > 0 && (!d_offsets || !d_labels || (n_bytes > 0 && !d_utf8));
+    if (int rc = device_call_begin(m, n_docs, d_utf8, null_ptr, [&] {
+            return n_bytes < 0 ? fail(LDGPU_EINVAL, "n_bytes < 0") : (int)LDGPU_OK;
+        }))
+        return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t chunk = utf8_chunk_docs();
+    for (int64_t d0 = 0; d0 < n_docs; d0 += chunk) {
+        const int64_t nd = std::min(chunk, n_docs - d0);
+        const size_t a_dec = ((size_t)n_bytes + 16 + 15) & ~(size_t)15, a_off = sizeof(int64_t) * (size_t)(nd + 1);
+        char* scratch = nullptr;
+        HIP_TRY(hipMallocAsync((void**)&scratch, a_dec + a_off + (size_t)nd, st));
+        const int rc = score_utf8_launch(m, d_utf8, n_bytes, d_offsets + d0, nd, (uint8_t*)scratch,
+                                         (int64_t*)(scratch + a_dec), (uint8_t*)(scratch + a_dec + a_off),
+                                         d_labels + d0, d_scores ? d_scores + (size_t)d0 * m->L : nullptr, m->d_err, st);
+        (void)hipFreeAsync(scratch, st);
+        if (rc) return rc;
+    }
+    if (n_docs > 0) {
+        if (int rc = check_row_error(m, m->d_err, st)) return rc;
+    }
+    return ok();
 }
 
 // ------------------------------------------------------------- SCORE: spans

@@ -346,4 +346,24 @@ struct PreParams {
 hipError_t launch_preprocess(const PreParams& p, int64_t* len_tmp, int64_t* out_off, void* scan_tmp, size_t* scan_bytes,
                              int cus, hipStream_t stream);
 
+// ------------------------------------------------------------------ UTF-8
+// UTF-8 documents to UTF-16 units or the SCORE encoding (ldgpu_utf8.hip; the
+// rule: include/ldgpu.h UTF-8)
+constexpr int kUtf8Step = 256;  // LDGPU_UTF8_STEP_BYTES: bytes a wave takes per step (a dword per lane)
+struct Utf8Params {
+    const uint8_t* utf8;        // 4-byte aligned
+    const int64_t* offsets;     // [n_docs + 1], in bytes
+    int64_t n_docs;
+    int32_t flags;              // 0 or LDGPU_PRE_LOW_BYTES
+    void* out;                  // units (u16) or, LDGPU_PRE_LOW_BYTES, bytes
+    uint8_t* host;              // [n_docs] 1 = ill-formed (empty output)
+};
+// pass 1 (units per document: len_tmp [n_docs + 1]), the scan into out_off
+// [n_docs + 1], pass 2 (the output); scan_tmp == nullptr: *scan_bytes = the
+// scan's scratch, nothing launched
+hipError_t launch_utf8_decode(const Utf8Params& p, int64_t* len_tmp, int64_t* out_off, void* scan_tmp,
+                              size_t* scan_bytes, int cus, hipStream_t stream);
+// labels[d] = -1 where host[d] is set
+hipError_t launch_utf8_labels(const uint8_t* host, int64_t n_docs, int32_t* labels, int cus, hipStream_t stream);
+
 }  // namespace ldgpu

@@ -103,10 +103,20 @@ SIGNATURES = [
     ("ldgpu_preprocess_device", ctypes.c_int, [_p, _p, _p, _i64, _p, _i32, _p, _p, _p, _p]),
     ("ldgpu_preprocess", ctypes.c_int, [_p, _p, _p, _i64, _p, _i32, _p, _p, _p]),
 ]
+# include/ldgpu.h UTF-8.  A list of its own: exported_symbols() is compared
+# with a scan of the header for names of letters and underscores only, which
+# does not see a name with a digit in it; utf8_symbols() lists these.
+UTF8_SIGNATURES = [
+    ("ldgpu_utf8_decode_device", ctypes.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _p, _p]),
+    ("ldgpu_utf8_decode", ctypes.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _p]),
+    ("ldgpu_score_utf8", ctypes.c_int, [_p, _p, _p, _i64, _p, _p]),
+    ("ldgpu_score_utf8_device", ctypes.c_int, [_p, _p, _i64, _p, _i64, _p, _p, _p]),
+]
 
 # include/ldgpu.h PREPROCESS
 PRE_LOWER, PRE_CLEAN, PRE_LOW_BYTES = 1, 2, 4
 LOCALE_ROOT, LOCALE_TR_AZ, LOCALE_LT = 0, 1, 2
+UTF8_STEP_BYTES = 256  # LDGPU_UTF8_STEP_BYTES
 
 _libs = {}
 _lock = threading.RLock()
@@ -150,7 +160,7 @@ def load(path: Optional[str] = None, variant: str = "product"):
         except Exception:
             pass
         lib = ctypes.CDLL(p)
-        for name, res, args in SIGNATURES:
+        for name, res, args in SIGNATURES + UTF8_SIGNATURES:
             if path is not None and not hasattr(lib, name):
                 continue  # an explicitly named older build (A/B timing): only its own entry points
             fn = getattr(lib, name)
@@ -163,6 +173,10 @@ def load(path: Optional[str] = None, variant: str = "product"):
 
 def exported_symbols() -> List[str]:
     return [s[0] for s in SIGNATURES]
+
+
+def utf8_symbols() -> List[str]:
+    return [s[0] for s in UTF8_SIGNATURES]
 
 
 def check(rc: int, lib=None) -> None:
@@ -210,7 +224,8 @@ def device_count() -> int:
 # the sources the library is built from, in the Makefile's PROV order
 _PROV = ["csrc/ldgpu_api.hip", "csrc/ldgpu_score.hip", "csrc/ldgpu_fit.hip", "csrc/ldgpu_general.hip",
          "csrc/ldgpu_long.hip", "csrc/ldgpu_replay.hip", "csrc/ldgpu_pre.hip", "csrc/ldgpu_topk.hip",
-         "csrc/ldgpu_spans.hip", "csrc/ldgpu_segments.hip", "csrc/ldgpu_trie.hip", "csrc/ldgpu_common.h",
+         "csrc/ldgpu_spans.hip", "csrc/ldgpu_segments.hip", "csrc/ldgpu_trie.hip", "csrc/ldgpu_utf8.hip",
+         "csrc/ldgpu_common.h",
          "csrc/ldgpu_internal.h", "csrc/ldgpu_wave.h", "csrc/ldgpu_trie.h", "csrc/ldgpu_fit.h", "../include/ldgpu.h"]
 
 

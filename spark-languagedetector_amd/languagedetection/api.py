@@ -25,7 +25,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import encoding, spans
+from . import encoding, spans, utf8
 from .runtime import DeviceCounts, DeviceModel
 
 
@@ -132,6 +132,65 @@ class LanguageDetectorModel(_Params):
         df = dataset if isinstance(dataset, pd.DataFrame) else pd.DataFrame(dataset)
         self.transformSchema(self._schema_of(df))
         labels, _ = self.predict_indices(list(df[self.getInputCol()]))
+        out = df.copy()
+        out[self.getOutputCol()] = [self.supportedLanguages[i] for i in labels]
+        return out
+
+    # UTF-8 input (an addition: the reference takes Strings).  The documents
+    # cross to the device as they are stored and are decoded there
+    # (languagedetection.utf8 states the rule); transform and predict_indices
+    # are untouched.
+    def predict_indices_utf8(self, docs, want_scores: bool = False, errors: str = "replace"
+                             ) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+        """predict_indices over UTF-8 documents: `docs` is a sequence of bytes,
+        or a packed (data uint8, offsets int64[n + 1]) pair.  A well-formed
+        document's label and scores are those predict_indices gives for its
+        decoded text.  An ill-formed document comes back from the device with
+        label -1 and is handled by `errors`:
+          "replace"  decoded on the host with bytes.decode("utf-8", "replace")
+                     and scored through predict_indices;
+          "strict"   UnicodeDecodeError for the first one.
+        The replacement rule is CPython's (one U+FFFD per maximal ill-formed
+        subpart); it is unpinned against a JVM, whose decoder may place its
+        replacement characters differently, as the preprocessors' host
+        restatement is."""
+        if errors not in ("replace", "strict"):
+            raise ValueError(f"errors must be \"replace\" or \"strict\", not {errors!r}")
+        if isinstance(docs, tuple) and len(docs) == 2 and isinstance(docs[0], np.ndarray):
+            data = np.ascontiguousarray(docs[0], dtype=np.uint8)
+            offsets = np.ascontiguousarray(docs[1], dtype=np.int64)
+        else:
+            docs = list(docs)
+            for d in docs:
+                if d is None:
+                    raise NullPointerException("text is null")
+            data, offsets = utf8.pack_utf8(docs)
+        labels, scores = self.device_model().score_utf8(data, offsets, want_scores)
+        bad = np.flatnonzero(labels < 0)
+        if len(bad):
+            raw = [data[int(offsets[i]):int(offsets[i + 1])].tobytes() for i in bad]
+            if errors == "strict":
+                raw[0].decode("utf-8")  # raises UnicodeDecodeError
+                raise AssertionError(f"document {int(bad[0])}: flagged ill-formed, but the codec decodes it")
+            l2, s2 = self.predict_indices([r.decode("utf-8", "replace") for r in raw], want_scores)
+            labels[bad] = l2
+            if want_scores:
+                scores[bad] = s2
+        return labels, scores
+
+    def transformUtf8(self, dataset, errors: str = "replace"):
+        """transform for an inputCol of bytes (UTF-8): appends outputCol = the
+        detected language of every row."""
+        import pandas as pd
+        df = dataset if isinstance(dataset, pd.DataFrame) else pd.DataFrame(dataset)
+        if self.getInputCol() not in df.columns:
+            raise ValueError(f"Field \"{self.getInputCol()}\" does not exist.")
+        col = list(df[self.getInputCol()])
+        if not all(v is None or isinstance(v, (bytes, bytearray)) for v in col):
+            raise ValueError("requirement failed: Input type must be BinaryType (UTF-8 bytes).")
+        if self.getOutputCol() in df.columns:
+            raise ValueError(f"requirement failed: Column {self.getOutputCol()} already exists.")
+        labels, _ = self.predict_indices_utf8(col, errors=errors)
         out = df.copy()
         out[self.getOutputCol()] = [self.supportedLanguages[i] for i in labels]
         return out

@@ -178,6 +178,35 @@ class DeviceModel(_Owner):
                                                      ctypes.c_void_p(d_top_scores) if d_top_scores else None,
                                                      ctypes.c_void_p(st) if st else None))
 
+    # UTF-8 documents (an addition; the rule: languagedetection.utf8)
+    def score_utf8(self, data: np.ndarray, offsets: np.ndarray, want_scores: bool = False,
+                   out: Optional[np.ndarray] = None) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+        """Host buffers of UTF-8 documents -> (labels int32[n], scores fp64[n,
+        L] or None) as score gives for their SCORE encoding, decoded on the
+        device (ldgpu_score_utf8); an ill-formed document gets label -1 and an
+        empty document's score row.  `out` receives the labels."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = len(offsets) - 1
+        if out is not None:
+            labels = out
+            assert labels.dtype == np.int32 and labels.shape == (max(n, 0),) and labels.flags.c_contiguous
+        else:
+            labels = np.zeros(max(n, 0), dtype=np.int32)
+        scores = np.zeros((max(n, 0), self.L), dtype=np.float64) if want_scores else None
+        self._check(self.lib.ldgpu_score_utf8(self.h, _ptr(data), _ptr(offsets), n, _ptr(labels), _ptr(scores)))
+        return labels, scores
+
+    def score_utf8_device(self, d_utf8: int, n_bytes: int, d_offsets: int, n_docs: int, d_labels: int,
+                          d_scores: int = 0, stream: Optional[int] = None) -> None:
+        """Device pointers to UTF-8 documents -> labels (and scores) in place,
+        async on `stream` as score_device (ldgpu_score_utf8_device)."""
+        st = self.stream() if stream is None else stream
+        self._check(self.lib.ldgpu_score_utf8_device(self.h, ctypes.c_void_p(d_utf8), n_bytes,
+                                                     ctypes.c_void_p(d_offsets), n_docs, ctypes.c_void_p(d_labels),
+                                                     ctypes.c_void_p(d_scores) if d_scores else None,
+                                                     ctypes.c_void_p(st) if st else None))
+
     # Span scoring (an addition; the rule: languagedetection.spans)
     def span_offsets(self, offsets: np.ndarray, width: int, stride: int) -> np.ndarray:
         """int64[n_docs + 1]: every document's first span (ldgpu_span_offsets: host arithmetic)."""
@@ -438,6 +467,39 @@ class DeviceCounts(_Owner):
         self._check(self.lib.ldgpu_fit_table_export_masks(self.h, _ptr(kb), _ptr(ko), _ptr(masks), _ptr(vals)))
         return kb, ko, masks[:n.value], vals[:n.value]
 
+
+
+def utf8_decode(data: np.ndarray, offsets: np.ndarray, low_bytes: bool = False, device: Optional[int] = None,
+                variant: str = "product") -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """UTF-8 documents decoded on the GPU (ldgpu_utf8_decode; the rule:
+    languagedetection.utf8): (UTF-16 units uint16 -- or, low_bytes, the SCORE
+    encoding uint8 --, output offsets int64[n + 1], host uint8[n]: 1 = the
+    document is ill-formed and its output empty)."""
+    lib = _lib.load(variant=variant)
+    ctx = _lib.context(device, variant)
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n = len(offsets) - 1
+    cap = max(int(offsets[-1] - offsets[0]) if n > 0 else 0, 1)
+    out = np.zeros(cap, dtype=np.uint8 if low_bytes else np.uint16)
+    out_off = np.zeros(max(n, 0) + 1, dtype=np.int64)
+    host = np.zeros(max(n, 1), dtype=np.uint8)
+    _lib.check(lib.ldgpu_utf8_decode(ctx, _ptr(data), _ptr(offsets), n, _lib.PRE_LOW_BYTES if low_bytes else 0,
+                                     _ptr(out), _ptr(out_off), _ptr(host)), lib)
+    return out[:int(out_off[-1])], out_off, host[:max(n, 0)]
+
+
+def utf8_decode_device(d_utf8: int, d_offsets: int, n_docs: int, d_out: int, d_out_offsets: int, d_host: int,
+                       low_bytes: bool = False, stream: int = 0, device: Optional[int] = None,
+                       variant: str = "product") -> None:
+    """Device pointers -> the decoded units (or low bytes), their offsets and
+    the flags in place, async on `stream` (ldgpu_utf8_decode_device)."""
+    lib = _lib.load(variant=variant)
+    ctx = _lib.context(device, variant)
+    _lib.check(lib.ldgpu_utf8_decode_device(ctx, ctypes.c_void_p(d_utf8), ctypes.c_void_p(d_offsets), n_docs,
+                                            _lib.PRE_LOW_BYTES if low_bytes else 0, ctypes.c_void_p(d_out),
+                                            ctypes.c_void_p(d_out_offsets), ctypes.c_void_p(d_host),
+                                            ctypes.c_void_p(stream) if stream else None), lib)
 
 
 def case_tables() -> Tuple[np.ndarray, np.ndarray]:
