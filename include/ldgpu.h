@@ -554,6 +554,105 @@ int ldgpu_score_utf8(ldgpu_model* model, const uint8_t* utf8, const int64_t* off
 int ldgpu_score_utf8_device(ldgpu_model* model, const uint8_t* d_utf8, int64_t n_bytes, const int64_t* d_offsets,
                             int64_t n_docs, int32_t* d_labels, double* d_scores, void* stream);
 
+/* ------------------------------------------- UTF-8: top-k, spans, segments */
+/* The top-k, span and segment forms of SCORE on UTF-8 documents, and every
+ * span's start as a byte position in its UTF-8 document.  (The names end in
+ * _utf.)  The rule:
+ *   - width and stride count UTF-16 units (= SCORE bytes), exactly as in
+ *     ldgpu_score_spans.
+ *   - A document's spans are those of ldgpu_span_offsets applied to its unit
+ *     count u: one span if u <= width, otherwise 1 + ceil((u - width) / stride).
+ *   - Well-formedness is ldgpu_utf8_decode's rule (Unicode Table 3-7).  An
+ *     ill-formed document counts as u = 0: it has one empty span.
+ *   - units[d] is u for a well-formed document and -1 for an ill-formed one.
+ *   - start[i], for span j of document d, is an int64 byte index relative to
+ *     the document's first byte: the index of the lead byte of the character
+ *     that unit j * stride belongs to.  If unit j * stride is the low surrogate
+ *     of a 4-byte character (the boundary splits the pair), it is that
+ *     character's lead byte.  A character's bytes therefore always belong to
+ *     one run, the one starting at or before its first unit.  At stride == 1
+ *     both units of a pair give the same start.  Span 0 of every document has
+ *     start 0; this includes an empty document's single span and an ill-formed
+ *     document's single span.  Starts are non-decreasing within a document.
+ *     Every start is < len for a non-empty well-formed document.
+ *   - Labels and score rows of a well-formed document's spans are bit for bit
+ *     those of ldgpu_score_spans, ldgpu_score_segments or ldgpu_score_topk on
+ *     its SCORE encoding, on every model layout.
+ *   - For an ill-formed document: its single span gets label -1 and the empty
+ *     document's score row; the top-k form gives -1 in all k label entries and
+ *     0.0 in the scores; the segment form gives -1.
+ *   - Byte runs (languagedetection.utf8.byte_runs) turn span labels into runs
+ *     in bytes.  Span j owns bytes [start[j], start[j+1]), the last span up to
+ *     the document's byte length.  Consecutive spans of one label merge.  Empty
+ *     runs are dropped.  This is the byte twin of languagedetection.spans.runs.
+ *
+ * Span offsets.  The span count depends on the unit count, which only a decode
+ * knows, so the span offsets come from the device: the device form runs the
+ * decoder's length pass and the span-offset arithmetic on the unit counts and
+ * reads nothing back (asynchronous on `stream`; d_utf8 4-byte aligned, offsets
+ * trusted, n_docs < 2^31 - 1 as in ldgpu_utf8_decode_device; d_units nullable).
+ * The host form copies the UTF-8 in, runs the device form and copies
+ * 8 (n_docs + 1) (+ 8 n_docs) bytes back; the offsets are checked as by
+ * ldgpu_score.  On the host route the UTF-8 therefore crosses PCIe twice: once
+ * here and once in the scoring call. */
+int ldgpu_span_offsets_utf(ldgpu_ctx* ctx, const uint8_t* utf8, const int64_t* offsets, int64_t n_docs,
+                           int32_t width, int32_t stride, int64_t* span_offsets /* [n_docs + 1] */,
+                           int64_t* units /* [n_docs], nullable */);
+int ldgpu_span_offsets_utf_device(ldgpu_ctx* ctx, const uint8_t* d_utf8, const int64_t* d_offsets, int64_t n_docs,
+                                  int32_t width, int32_t stride, int64_t* d_span_offsets,
+                                  int64_t* d_units /* nullable */, void* stream);
+
+/* ldgpu_score_topk on UTF-8 documents.  Argument checks, LDGPU_EROWLEN, thread
+ * safety and the pipeline are those of ldgpu_score_topk; the 2^28 limit applies
+ * to a document's UTF-8 length.  Each chunk is decoded on the device and
+ * scored and selected from the decoded bytes. */
+int ldgpu_score_topk_utf(ldgpu_model* model, const uint8_t* utf8, const int64_t* offsets, int64_t n_docs,
+                         int32_t k, int32_t* out_top_labels, double* out_top_scores /* nullable */);
+/* Device-resident variant, asynchronous on `stream` under the rules of
+ * ldgpu_score_utf8_device: d_utf8 4-byte aligned, n_bytes >= d_offsets[n_docs],
+ * offsets trusted.  The call decodes into stream-ordered scratch: n_bytes of
+ * low bytes, plus the offsets and flags of all n_docs documents;
+ * n_docs >= 2^31 - 1 is LDGPU_EUNSUPPORTED.  Nothing is read back. */
+int ldgpu_score_topk_utf_device(ldgpu_model* model, const uint8_t* d_utf8, int64_t n_bytes,
+                                const int64_t* d_offsets, int64_t n_docs, int32_t k, int32_t* d_top_labels,
+                                double* d_top_scores, void* stream);
+
+/* ldgpu_score_spans on UTF-8 documents.  span_offsets [n_docs + 1] is the
+ * output of the span-offset call above for the same width and stride; it is
+ * checked (NULL, a first entry other than 0, a decrease, a document without a
+ * span: LDGPU_EINVAL).  out_labels [n_spans], out_scores nullable
+ * [n_spans][n_langs], out_starts nullable [n_spans] (the starts of the rule
+ * above), n_spans = span_offsets[n_docs].  Argument checks, LDGPU_EROWLEN,
+ * thread safety and the absent document-length limit are those of
+ * ldgpu_score_spans.  The pipeline's chunks end at document boundaries, cut as
+ * ldgpu_score_segments cuts them: whole documents within the span budget (with
+ * scores also the top-k call's 256 MiB of score rows) and 64 MiB of UTF-8
+ * bytes, one at least; the chunk is decoded on the device and its spans are
+ * gathered and scored from the decoded bytes in span chunks. */
+int ldgpu_score_spans_utf(ldgpu_model* model, const uint8_t* utf8, const int64_t* offsets, int64_t n_docs,
+                          int32_t width, int32_t stride, const int64_t* span_offsets, int32_t* out_labels,
+                          double* out_scores /* nullable */, int64_t* out_starts /* nullable */);
+/* Device-resident variant, asynchronous on `stream` under the rules of the
+ * top-k variant above (alignment, scratch, the n_docs limit) and of
+ * ldgpu_score_spans_device: n_spans may over-estimate d_span_offsets[n_docs];
+ * an index at or beyond it gets label 0 and start 0.  With d_starts NULL no
+ * start is computed. */
+int ldgpu_score_spans_utf_device(ldgpu_model* model, const uint8_t* d_utf8, int64_t n_bytes,
+                                 const int64_t* d_offsets, int64_t n_docs, int32_t width, int32_t stride,
+                                 const int64_t* d_span_offsets, int64_t n_spans, int32_t* d_labels,
+                                 double* d_scores /* nullable */, int64_t* d_starts /* nullable */, void* stream);
+
+/* ldgpu_score_segments on UTF-8 documents: span_offsets, out_starts, checks and
+ * chunks as in the span form above, the penalty check of
+ * ldgpu_score_segments. */
+int ldgpu_score_segments_utf(ldgpu_model* model, const uint8_t* utf8, const int64_t* offsets, int64_t n_docs,
+                             int32_t width, int32_t stride, double penalty, const int64_t* span_offsets,
+                             int32_t* out_labels, int64_t* out_starts /* nullable */);
+int ldgpu_score_segments_utf_device(ldgpu_model* model, const uint8_t* d_utf8, int64_t n_bytes,
+                                    const int64_t* d_offsets, int64_t n_docs, int32_t width, int32_t stride,
+                                    double penalty, const int64_t* d_span_offsets, int64_t n_spans,
+                                    int32_t* d_labels, int64_t* d_starts /* nullable */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -256,6 +256,9 @@ struct ScoreStage {
     // UTF-8 calls (ldgpu_score_utf8): the chunk's decoded SCORE bytes, their
     // offsets and the ill-formed flags (`bytes` and `offsets` hold the UTF-8)
     DevBuf dec, dec_offsets, dec_host;
+    // UTF-8 span and segment calls: the chunk's span starts (a call's third output)
+    DevBuf starts;
+    HostBuf h_starts;
     int64_t d0 = 0, nd = 0;  // the chunk in flight: its first item and their number
     bool busy = false;
 };
@@ -357,9 +360,9 @@ void pipe_destroy(ScorePipe* pp) {
     for (auto& st : pp->stage) {
         if (st.stream) (void)hipStreamSynchronize(st.stream);
         for (DevBuf* b : {&st.bytes, &st.offsets, &st.labels, &st.scores, &st.top_labels, &st.top_scores, &st.dec,
-                          &st.dec_offsets, &st.dec_host})
+                          &st.dec_offsets, &st.dec_host, &st.starts})
             b->release();
-        for (HostBuf* b : {&st.h_bytes, &st.h_offsets, &st.h_labels, &st.h_scores}) b->release();
+        for (HostBuf* b : {&st.h_bytes, &st.h_offsets, &st.h_labels, &st.h_scores, &st.h_starts}) b->release();
         if (st.done) (void)hipEventDestroy(st.done);
         if (st.stream) (void)hipStreamDestroy(st.stream);
     }
@@ -2342,7 +2345,8 @@ struct ScoreCall {
     int64_t n_docs;
     const int64_t* span_offsets;  // the span form's items: [n_docs + 1], else nullptr
     int64_t n_items;              // documents, or spans
-    PipeOut out[2];               // [0] labels (memcpy), [1] score rows (par_memcpy)
+    PipeOut out[3];               // [0] labels (memcpy), [1] score rows (par_memcpy), [2] the UTF-8 span
+                                  // forms' starts (memcpy); an entry left out is not asked for
 };
 
 // Two-stage pipeline over chunks of items, one stream per stage: while the GPU
@@ -2364,6 +2368,8 @@ int run_score_pipe(ldgpu_model* m, ScorePipe* pp, const ScoreCall& c, Cut cut, L
         const PipeOut &lab = c.out[0], &sc = c.out[1];
         memcpy((char*)lab.base + st.d0 * lab.item, (st.*lab.host).p, lab.item * st.nd);
         if (sc.base) par_memcpy((char*)sc.base + st.d0 * sc.item, (st.*sc.host).p, sc.item * st.nd);
+        if (const PipeOut& sta = c.out[2]; sta.base)
+            memcpy((char*)sta.base + st.d0 * sta.item, (st.*sta.host).p, sta.item * st.nd);
         return LDGPU_OK;
     };
     // one chunk's copies and launch on stage st; an error returns without
@@ -2395,8 +2401,8 @@ int run_score_pipe(ldgpu_model* m, ScorePipe* pp, const ScoreCall& c, Cut cut, L
         // (class mode included: its replay of ambiguous documents reads no
         // count back, so the staging of the next chunk still overlaps)
         if (int r = launch(st, ch, pp->d_err)) return r;
-        void* dst[2] = {nullptr, nullptr};
-        for (int i = 0; i < 2; ++i) {
+        void* dst[3] = {nullptr, nullptr, nullptr};
+        for (int i = 0; i < 3; ++i) {
             const PipeOut& o = c.out[i];
             if (!o.base) continue;
             dst[i] = (char*)o.base + ch.i0 * o.item;
@@ -2405,7 +2411,7 @@ int run_score_pipe(ldgpu_model* m, ScorePipe* pp, const ScoreCall& c, Cut cut, L
                 dst[i] = (st.*o.host).p;
             }
         }
-        for (int i = 0; i < 2; ++i)
+        for (int i = 0; i < 3; ++i)
             if (dst[i])
                 HIP_TRY(hipMemcpyAsync(dst[i], (st.*c.out[i].dev).p, c.out[i].item * n, hipMemcpyDeviceToHost,
                                        st.stream));
@@ -2958,6 +2964,386 @@ extern "C" int ldgpu_score_segments(ldgpu_model* m, const uint8_t* bytes, const 
         return segments_launch(m, sp, penalty, ch.i1 - ch.i0, (int32_t*)st.labels.p, d_err, st.stream);
     };
     return with_pipe(m, [&](ScorePipe* pp) { return run_score_pipe(m, pp, call, cut, launch); });
+}
+
+// ------------------------------------- SCORE: UTF-8 top-k, spans, segments
+// The three remaining forms on UTF-8 documents (the rule: include/ldgpu.h
+// UTF-8: top-k, spans, segments).  Every form decodes to the SCORE encoding
+// first (ldgpu_utf8.hip) and then runs its twin's own launch on the decoded
+// corpus; the span starts come from a kernel over the UTF-8 itself, the labels
+// of ill-formed documents are set last.
+namespace {
+int check_utf_docs(int64_t n_docs) {
+    if (n_docs >= (int64_t)std::numeric_limits<int>::max())
+        return fail(LDGPU_EUNSUPPORTED, "%lld documents in one call (the scan takes < 2^31)", (long long)n_docs);
+    return LDGPU_OK;
+}
+
+// a device-form call's decode scratch on st: n_bytes (+ slack) of low bytes,
+// the decoded offsets and the flags of n_docs documents
+struct UtfScratch {
+    char* p = nullptr;
+    uint8_t* dec = nullptr;
+    int64_t* dec_off = nullptr;
+    uint8_t* host = nullptr;
+};
+int utf_scratch_decode(ldgpu_model* m, const uint8_t* d_utf8, int64_t n_bytes, const int64_t* d_offsets,
+                       int64_t n_docs, UtfScratch* s, hipStream_t st) {
+    const size_t a_dec = ((size_t)n_bytes + 16 + 255) & ~(size_t)255, a_off = up256(sizeof(int64_t) * (size_t)(n_docs + 1));
+    HIP_TRY(hipMallocAsync((void**)&s->p, a_dec + a_off + (size_t)n_docs + 16, st));
+    s->dec = (uint8_t*)s->p;
+    s->dec_off = (int64_t*)(s->p + a_dec);
+    s->host = (uint8_t*)(s->p + a_dec + a_off);
+    const int rc = utf8_decode_launch(m->ctx->cus, d_utf8, d_offsets, n_docs, LDGPU_PRE_LOW_BYTES, s->dec, s->dec_off,
+                                      s->host, st);
+    if (rc) (void)hipFreeAsync(s->p, st);
+    return rc;
+}
+
+// after the decoded corpus is scored: the span starts (d_starts nullable: no
+// work at all) and the -1 labels of the ill-formed documents
+int utf_span_finish(ldgpu_model* m, const uint8_t* d_utf8, const int64_t* d_offsets, int64_t n_docs,
+                    const uint8_t* d_host, const int64_t* d_span_offsets, int64_t n_spans, int32_t stride,
+                    int32_t* d_labels, int64_t* d_starts, hipStream_t st) {
+    if (d_starts) {
+        Utf8StartParams q{};
+        q.utf8 = d_utf8;
+        q.offsets = d_offsets;
+        q.n_docs = n_docs;
+        q.host = d_host;
+        q.span_offsets = d_span_offsets;
+        q.n_spans = n_spans;
+        q.stride = stride;
+        q.starts = d_starts;
+        HIP_TRY(launch_utf8_starts(q, m->ctx->cus, st));
+    }
+    HIP_TRY(launch_utf8_span_labels(d_host, d_span_offsets, n_docs, n_spans, d_labels, m->ctx->cus, st));
+    return LDGPU_OK;
+}
+
+// the spans [0, n_spans) of the corpus sp describes, chunk after chunk
+int span_chunks(ldgpu_model* m, SpanParams sp, int64_t n_spans, int64_t chunk, int32_t* d_labels, double* d_scores,
+                int32_t* d_err, hipStream_t st) {
+    for (int64_t g0 = 0; g0 < n_spans; g0 += chunk) {
+        sp.g0 = g0;
+        sp.nc = std::min(chunk, n_spans - g0);
+        if (int rc = span_chunk(m, sp, d_labels + g0, d_scores ? d_scores + g0 * m->L : nullptr, d_err, st)) return rc;
+    }
+    return LDGPU_OK;
+}
+
+// the host forms' span_offsets: [n_docs + 1] from 0, every document a span
+int check_span_offsets(const int64_t* span_offsets, int64_t n_docs) {
+    if (!span_offsets) return fail(LDGPU_EINVAL, "span_offsets is NULL");
+    if (span_offsets[0] != 0) return fail(LDGPU_EINVAL, "span_offsets[0] = %lld, not 0", (long long)span_offsets[0]);
+    for (int64_t d = 0; d < n_docs; ++d)
+        if (span_offsets[d + 1] <= span_offsets[d])
+            return fail(LDGPU_EINVAL, "span_offsets decrease or leave document %lld without a span", (long long)d);
+    return LDGPU_OK;
+}
+
+// whole documents from the one whose first span is g0: as many as fit `budget`
+// spans and kScoreChunkBytes of source bytes, one at least (ldgpu_score_segments' cut)
+auto span_doc_chunks(const int64_t* offsets, const int64_t* soff, int64_t n_docs, int64_t budget) {
+    return [=](int64_t g0) {
+        const int64_t d0 = (int64_t)(std::upper_bound(soff, soff + n_docs, g0) - soff) - 1;
+        int64_t d1 = d0 + 1;
+        while (d1 < n_docs && soff[d1 + 1] - soff[d0] <= budget && offsets[d1 + 1] - offsets[d0] <= kScoreChunkBytes)
+            ++d1;
+        return PipeChunk{soff[d0], soff[d1], offsets[d0], offsets[d1], d0, d1 - d0};
+    };
+}
+
+// a host chunk's UTF-8 (st.bytes, st.offsets) decoded into the stage's buffers
+int stage_decode(ldgpu_model* m, ScoreStage& st, int64_t nd, int64_t nb) {
+    HIP_TRY(st.dec.ensure((size_t)nb + 16));
+    HIP_TRY(st.dec_offsets.ensure(sizeof(int64_t) * (size_t)(nd + 1)));
+    HIP_TRY(st.dec_host.ensure((size_t)nd));
+    return utf8_decode_launch(m->ctx->cus, (const uint8_t*)st.bytes.p, (const int64_t*)st.offsets.p, nd,
+                              LDGPU_PRE_LOW_BYTES, st.dec.p, (int64_t*)st.dec_offsets.p, (uint8_t*)st.dec_host.p,
+                              st.stream);
+}
+}  // namespace
+
+extern "C" int ldgpu_span_offsets_utf_device(ldgpu_ctx* ctx, const uint8_t* d_utf8, const int64_t* d_offsets,
+                                             int64_t n_docs, int32_t width, int32_t stride, int64_t* d_span_offsets,
+                                             int64_t* d_units, void* stream) {
+    if (!ctx) return fail(LDGPU_EINVAL, "context is NULL");
+    if (n_docs < 0) return fail(LDGPU_EINVAL, "n_docs < 0");
+    if (int rc = check_span_args(width, stride)) return rc;
+    if (!d_span_offsets || (n_docs > 0 && !d_offsets)) return fail(LDGPU_EINVAL, "device pointer is NULL");
+    if (((uintptr_t)d_utf8 & 3) != 0) return fail(LDGPU_EINVAL, "d_utf8 must be 4-byte aligned");
+    if (int rc = check_utf_docs(n_docs)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(ctx->device));
+    Utf8Params p{};
+    p.utf8 = d_utf8;
+    p.offsets = d_offsets;
+    p.n_docs = n_docs;
+    size_t scan_bytes = 0;
+    HIP_TRY(launch_utf8_span_offsets(p, width, stride, nullptr, nullptr, nullptr, nullptr, &scan_bytes, ctx->cus, st));
+    const size_t n_len = up256(sizeof(int64_t) * (size_t)(n_docs + 1)), n_scan = up256(scan_bytes);
+    char* scratch = nullptr;
+    HIP_TRY(hipMallocAsync((void**)&scratch, n_len + n_scan + (size_t)n_docs + 16, st));
+    p.host = (uint8_t*)(scratch + n_len + n_scan);
+    const hipError_t e = launch_utf8_span_offsets(p, width, stride, (int64_t*)scratch, d_span_offsets, d_units,
+                                                  scratch + n_len, &scan_bytes, ctx->cus, st);
+    (void)hipFreeAsync(scratch, st);
+    HIP_TRY(e);
+    return ok();
+}
+
+extern "C" int ldgpu_span_offsets_utf(ldgpu_ctx* ctx, const uint8_t* utf8, const int64_t* offsets, int64_t n_docs,
+                                      int32_t width, int32_t stride, int64_t* span_offsets, int64_t* units) {
+    if (!ctx) return fail(LDGPU_EINVAL, "context is NULL");
+    if (int rc = check_offsets(offsets, n_docs)) return rc;
+    if (int rc = check_span_args(width, stride)) return rc;
+    if (!span_offsets) return fail(LDGPU_EINVAL, "span_offsets is NULL");
+    const int64_t b0 = n_docs > 0 ? offsets[0] : 0, nb = n_docs > 0 ? offsets[n_docs] - b0 : 0;
+    if (nb > 0 && !utf8) return fail(LDGPU_EINVAL, "utf8 is NULL");
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::vector<int64_t> off0((size_t)n_docs + 1);
+    for (int64_t i = 0; i <= n_docs; ++i) off0[(size_t)i] = n_docs > 0 ? offsets[i] - b0 : 0;
+    // one device block: bytes, offsets (in, span), units
+    const size_t a_in = ((size_t)nb + 15) & ~(size_t)15, a_off = sizeof(int64_t) * ((size_t)n_docs + 1);
+    uint8_t* d = nullptr;
+    HIP_TRY(hipMalloc((void**)&d, a_in + 3 * a_off + 16));
+    int64_t* d_off = (int64_t*)(d + a_in);
+    int64_t* d_soff = (int64_t*)(d + a_in + a_off);
+    int64_t* d_units = (int64_t*)(d + a_in + 2 * a_off);
+    hipStream_t st = ctx->stream;
+    int rc = LDGPU_OK;
+    hipError_t e = hipSuccess;
+    {
+        std::lock_guard<std::mutex> lock(ctx->mu);  // the context's stream
+        if (nb) e = hipMemcpyAsync(d, utf8 + b0, (size_t)nb, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_off, off0.data(), a_off, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+            rc = ldgpu_span_offsets_utf_device(ctx, d, d_off, n_docs, width, stride, d_soff, units ? d_units : nullptr, st);
+        if (e == hipSuccess && !rc) e = hipMemcpyAsync(span_offsets, d_soff, a_off, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && !rc && units && n_docs)
+            e = hipMemcpyAsync(units, d_units, sizeof(int64_t) * (size_t)n_docs, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && !rc) e = hipStreamSynchronize(st);
+    }
+    (void)hipFree(d);
+    if (rc) return rc;
+    HIP_TRY(e);
+    return ok();
+}
+
+extern "C" int ldgpu_score_topk_utf_device(ldgpu_model* m, const uint8_t* d_utf8, int64_t n_bytes,
+                                           const int64_t* d_offsets, int64_t n_docs, int32_t k, int32_t* d_top_labels,
+                                           double* d_top_scores, void* stream) {
+    const bool null_ptr = n_docs > 0 && (!d_offsets || !d_top_labels || (n_bytes > 0 && !d_utf8));
+    if (int rc = device_call_begin(m, n_docs, d_utf8, null_ptr, [&] {
+            if (n_bytes < 0) return fail(LDGPU_EINVAL, "n_bytes < 0");
+            if (int r = check_topk(m, k)) return r;
+            return check_utf_docs(n_docs);
+        }))
+        return rc;
+    if (n_docs == 0) return ok();
+    hipStream_t st = (hipStream_t)stream;
+    UtfScratch s;
+    if (int rc = utf_scratch_decode(m, d_utf8, n_bytes, d_offsets, n_docs, &s, st)) return rc;
+    int rc = LDGPU_OK;
+    hipError_t e = hipSuccess;
+    const int64_t chunk = topk_chunk_docs(m->L);
+    for (int64_t d0 = 0; d0 < n_docs && !rc && e == hipSuccess; d0 += chunk) {
+        const int64_t nd = std::min(chunk, n_docs - d0);
+        const size_t score_bytes = sizeof(double) * (size_t)nd * m->L;
+        char* scratch = nullptr;
+        e = hipMallocAsync((void**)&scratch, score_bytes + sizeof(int32_t) * (size_t)nd, st);
+        if (e != hipSuccess) break;
+        rc = score_launch(m, s.dec, n_bytes, s.dec_off + d0, nd, (int32_t*)(scratch + score_bytes), (double*)scratch,
+                          m->d_err, st);
+        if (!rc)
+            e = topk_select(m, (const double*)scratch, nd, k, d_top_labels + d0 * k,
+                            d_top_scores ? d_top_scores + d0 * k : nullptr, st);
+        (void)hipFreeAsync(scratch, st);
+    }
+    if (!rc && e == hipSuccess)
+        e = launch_utf8_topk_labels(s.host, n_docs, k, d_top_labels, d_top_scores, m->ctx->cus, st);
+    (void)hipFreeAsync(s.p, st);
+    if (rc) return rc;
+    HIP_TRY(e);
+    if (int r = check_row_error(m, m->d_err, st)) return r;
+    return ok();
+}
+
+extern "C" int ldgpu_score_topk_utf(ldgpu_model* m, const uint8_t* utf8, const int64_t* offsets, int64_t n_docs,
+                                    int32_t k, int32_t* out_top_labels, double* out_top_scores) {
+    if (int rc = check_host_call(m, utf8, offsets, n_docs, out_top_labels, "out_top_labels", true,
+                                 [&] { return check_topk(m, k); }))
+        return rc;
+    if (n_docs == 0) return ok();
+    const ScoreCall call{utf8, offsets, n_docs, nullptr, n_docs,
+                         {{&ScoreStage::top_labels, &ScoreStage::h_labels, out_top_labels, sizeof(int32_t) * k},
+                          {&ScoreStage::top_scores, &ScoreStage::h_scores, out_top_scores, sizeof(double) * k}}};
+    auto launch = [&](ScoreStage& st, const PipeChunk& ch, int32_t* d_err) -> int {
+        const int64_t nd = ch.i1 - ch.i0, nb = ch.hi - ch.lo;
+        HIP_TRY(st.labels.ensure(sizeof(int32_t) * nd));
+        HIP_TRY(st.scores.ensure(sizeof(double) * nd * m->L));
+        if (int r = stage_decode(m, st, nd, nb)) return r;
+        if (int r = score_launch(m, (const uint8_t*)st.dec.p, nb, (const int64_t*)st.dec_offsets.p, nd,
+                                 (int32_t*)st.labels.p, (double*)st.scores.p, d_err, st.stream))
+            return r;
+        double* top_scores = out_top_scores ? (double*)st.top_scores.p : nullptr;
+        HIP_TRY(topk_select(m, (const double*)st.scores.p, nd, k, (int32_t*)st.top_labels.p, top_scores, st.stream));
+        HIP_TRY(launch_utf8_topk_labels((const uint8_t*)st.dec_host.p, nd, k, (int32_t*)st.top_labels.p, top_scores,
+                                        m->ctx->cus, st.stream));
+        return LDGPU_OK;
+    };
+    const int64_t max_docs = std::min(score_chunk_docs(), topk_chunk_docs(m->L));
+    return with_pipe(m, [&](ScorePipe* pp) {
+        return run_score_pipe(m, pp, call, doc_chunks(offsets, n_docs, max_docs), launch);
+    });
+}
+
+extern "C" int ldgpu_score_spans_utf_device(ldgpu_model* m, const uint8_t* d_utf8, int64_t n_bytes,
+                                            const int64_t* d_offsets, int64_t n_docs, int32_t width, int32_t stride,
+                                            const int64_t* d_span_offsets, int64_t n_spans, int32_t* d_labels,
+                                            double* d_scores, int64_t* d_starts, void* stream) {
+    const bool null_ptr = n_spans > 0 && (!d_offsets || !d_span_offsets || !d_labels || (n_bytes > 0 && !d_utf8));
+    if (int rc = device_call_begin(m, n_docs, d_utf8, null_ptr, [&] {
+            if (n_bytes < 0) return fail(LDGPU_EINVAL, "n_bytes < 0");
+            if (n_spans < 0) return fail(LDGPU_EINVAL, "n_spans < 0");
+            if (int r = check_span_args(width, stride)) return r;
+            return check_utf_docs(n_docs);
+        }))
+        return rc;
+    if (n_spans == 0) return ok();
+    hipStream_t st = (hipStream_t)stream;
+    UtfScratch s;
+    if (int rc = utf_scratch_decode(m, d_utf8, n_bytes, d_offsets, n_docs, &s, st)) return rc;
+    SpanParams sp{};
+    sp.bytes = s.dec;
+    sp.n_bytes = n_bytes;
+    sp.offsets = s.dec_off;
+    sp.n_docs = n_docs;
+    sp.span_offsets = d_span_offsets;
+    sp.width = width;
+    sp.stride = stride;
+    int rc = span_chunks(m, sp, n_spans, span_chunk_spans(width), d_labels, d_scores, m->d_err, st);
+    if (!rc)
+        rc = utf_span_finish(m, d_utf8, d_offsets, n_docs, s.host, d_span_offsets, n_spans, stride, d_labels, d_starts,
+                             st);
+    (void)hipFreeAsync(s.p, st);
+    if (rc) return rc;
+    if (int r = check_row_error(m, m->d_err, st)) return r;
+    return ok();
+}
+
+extern "C" int ldgpu_score_spans_utf(ldgpu_model* m, const uint8_t* utf8, const int64_t* offsets, int64_t n_docs,
+                                     int32_t width, int32_t stride, const int64_t* span_offsets, int32_t* out_labels,
+                                     double* out_scores, int64_t* out_starts) {
+    if (int rc = check_host_call(m, utf8, offsets, n_docs, out_labels, "out_labels", false,
+                                 [&] { return check_span_args(width, stride); }))
+        return rc;
+    if (n_docs == 0) return ok();
+    if (int rc = check_span_offsets(span_offsets, n_docs)) return rc;
+    const int64_t n_spans = span_offsets[n_docs];
+    const ScoreCall call{utf8, offsets, n_docs, span_offsets, n_spans,
+                         {{&ScoreStage::labels, &ScoreStage::h_labels, out_labels, sizeof(int32_t)},
+                          {&ScoreStage::scores, &ScoreStage::h_scores, out_scores, sizeof(double) * m->L},
+                          {&ScoreStage::starts, &ScoreStage::h_starts, out_starts, sizeof(int64_t)}}};
+    // (with scores the stage's score buffer bounds a chunk too, as in the span form)
+    int64_t budget = span_chunk_spans(width);
+    if (out_scores) budget = std::min(budget, topk_chunk_docs(m->L));
+    auto launch = [&](ScoreStage& st, const PipeChunk& ch, int32_t* d_err) -> int {
+        const int64_t nd = ch.n_docs, nb = ch.hi - ch.lo, n = ch.i1 - ch.i0;
+        if (int r = stage_decode(m, st, nd, nb)) return r;
+        const int64_t* soff = (const int64_t*)st.offsets.p + nd + 1;
+        SpanParams sp{};
+        sp.bytes = (const uint8_t*)st.dec.p;
+        sp.n_bytes = nb;
+        sp.offsets = (const int64_t*)st.dec_offsets.p;
+        sp.n_docs = nd;
+        sp.span_offsets = soff;
+        sp.width = width;
+        sp.stride = stride;
+        if (int r = span_chunks(m, sp, n, budget, (int32_t*)st.labels.p, out_scores ? (double*)st.scores.p : nullptr,
+                                d_err, st.stream))
+            return r;
+        return utf_span_finish(m, (const uint8_t*)st.bytes.p, (const int64_t*)st.offsets.p, nd,
+                               (const uint8_t*)st.dec_host.p, soff, n, stride, (int32_t*)st.labels.p,
+                               out_starts ? (int64_t*)st.starts.p : nullptr, st.stream);
+    };
+    return with_pipe(m, [&](ScorePipe* pp) {
+        return run_score_pipe(m, pp, call, span_doc_chunks(offsets, span_offsets, n_docs, budget), launch);
+    });
+}
+
+extern "C" int ldgpu_score_segments_utf_device(ldgpu_model* m, const uint8_t* d_utf8, int64_t n_bytes,
+                                               const int64_t* d_offsets, int64_t n_docs, int32_t width,
+                                               int32_t stride, double penalty, const int64_t* d_span_offsets,
+                                               int64_t n_spans, int32_t* d_labels, int64_t* d_starts, void* stream) {
+    const bool null_ptr = n_spans > 0 && (!d_offsets || !d_span_offsets || !d_labels || (n_bytes > 0 && !d_utf8));
+    if (int rc = device_call_begin(m, n_docs, d_utf8, null_ptr, [&] {
+            if (n_bytes < 0) return fail(LDGPU_EINVAL, "n_bytes < 0");
+            if (n_spans < 0) return fail(LDGPU_EINVAL, "n_spans < 0");
+            if (int r = check_span_args(width, stride)) return r;
+            if (int r = check_penalty(penalty)) return r;
+            return check_utf_docs(n_docs);
+        }))
+        return rc;
+    if (n_spans == 0) return ok();
+    hipStream_t st = (hipStream_t)stream;
+    UtfScratch s;
+    if (int rc = utf_scratch_decode(m, d_utf8, n_bytes, d_offsets, n_docs, &s, st)) return rc;
+    SpanParams sp{};
+    sp.bytes = s.dec;
+    sp.n_bytes = n_bytes;
+    sp.offsets = s.dec_off;
+    sp.n_docs = n_docs;
+    sp.span_offsets = d_span_offsets;
+    sp.width = width;
+    sp.stride = stride;
+    int rc = segments_launch(m, sp, penalty, n_spans, d_labels, m->d_err, st);
+    if (!rc)
+        rc = utf_span_finish(m, d_utf8, d_offsets, n_docs, s.host, d_span_offsets, n_spans, stride, d_labels, d_starts,
+                             st);
+    (void)hipFreeAsync(s.p, st);
+    if (rc) return rc;
+    if (int r = check_row_error(m, m->d_err, st)) return r;
+    return ok();
+}
+
+extern "C" int ldgpu_score_segments_utf(ldgpu_model* m, const uint8_t* utf8, const int64_t* offsets, int64_t n_docs,
+                                        int32_t width, int32_t stride, double penalty, const int64_t* span_offsets,
+                                        int32_t* out_labels, int64_t* out_starts) {
+    if (int rc = check_host_call(m, utf8, offsets, n_docs, out_labels, "out_labels", false, [&] {
+            if (int r = check_span_args(width, stride)) return r;
+            return check_penalty(penalty);
+        }))
+        return rc;
+    if (n_docs == 0) return ok();
+    if (int rc = check_span_offsets(span_offsets, n_docs)) return rc;
+    const int64_t n_spans = span_offsets[n_docs];
+    const ScoreCall call{utf8, offsets, n_docs, span_offsets, n_spans,
+                         {{&ScoreStage::labels, &ScoreStage::h_labels, out_labels, sizeof(int32_t)},
+                          {&ScoreStage::scores, &ScoreStage::h_scores, nullptr, 0},
+                          {&ScoreStage::starts, &ScoreStage::h_starts, out_starts, sizeof(int64_t)}}};
+    auto launch = [&](ScoreStage& st, const PipeChunk& ch, int32_t* d_err) -> int {
+        const int64_t nd = ch.n_docs, nb = ch.hi - ch.lo, n = ch.i1 - ch.i0;
+        if (int r = stage_decode(m, st, nd, nb)) return r;
+        const int64_t* soff = (const int64_t*)st.offsets.p + nd + 1;
+        SpanParams sp{};
+        sp.bytes = (const uint8_t*)st.dec.p;
+        sp.n_bytes = nb;
+        sp.offsets = (const int64_t*)st.dec_offsets.p;
+        sp.n_docs = nd;
+        sp.span_offsets = soff;
+        sp.width = width;
+        sp.stride = stride;
+        if (int r = segments_launch(m, sp, penalty, n, (int32_t*)st.labels.p, d_err, st.stream)) return r;
+        return utf_span_finish(m, (const uint8_t*)st.bytes.p, (const int64_t*)st.offsets.p, nd,
+                               (const uint8_t*)st.dec_host.p, soff, n, stride, (int32_t*)st.labels.p,
+                               out_starts ? (int64_t*)st.starts.p : nullptr, st.stream);
+    };
+    return with_pipe(m, [&](ScorePipe* pp) {
+        return run_score_pipe(m, pp, call, span_doc_chunks(offsets, span_offsets, n_docs, span_chunk_spans(width)),
+                              launch);
+    });
 }
 
 // ---------------------------------------------------------------------- FIT

@@ -366,4 +366,32 @@ hipError_t launch_utf8_decode(const Utf8Params& p, int64_t* len_tmp, int64_t* ou
 // labels[d] = -1 where host[d] is set
 hipError_t launch_utf8_labels(const uint8_t* host, int64_t n_docs, int32_t* labels, int cus, hipStream_t stream);
 
+// Spans of UTF-8 documents (the rule: include/ldgpu.h UTF-8: top-k, spans,
+// segments).  Pass 1 of the decoder (len_tmp [n_docs + 1], p.host), then, in
+// place, every document's span count from its unit count -- units (nullable)
+// [n_docs] gets the unit count, -1 for an ill-formed document -- and the scan
+// into span_offsets [n_docs + 1]; scan_tmp == nullptr: *scan_bytes = the
+// scan's scratch, nothing launched.  p.out and p.flags are not used.
+hipError_t launch_utf8_span_offsets(const Utf8Params& p, int32_t width, int32_t stride, int64_t* len_tmp,
+                                    int64_t* span_offsets, int64_t* units, void* scan_tmp, size_t* scan_bytes,
+                                    int cus, hipStream_t stream);
+// Every span's start as a byte index into its UTF-8 document
+struct Utf8StartParams {
+    const uint8_t* utf8;          // 4-byte aligned
+    const int64_t* offsets;       // [n_docs + 1], in bytes
+    int64_t n_docs;
+    const uint8_t* host;          // [n_docs] the decoder's flags
+    const int64_t* span_offsets;  // [n_docs + 1]
+    int64_t n_spans;              // entries of starts (>= span_offsets[n_docs])
+    int32_t stride;               // in units
+    int64_t* starts;              // out [n_spans]
+};
+hipError_t launch_utf8_starts(const Utf8StartParams& p, int cus, hipStream_t stream);
+// labels[span_offsets[d]] = -1 where host[d] is set (span indices outside [0, n_spans) are left alone)
+hipError_t launch_utf8_span_labels(const uint8_t* host, const int64_t* span_offsets, int64_t n_docs, int64_t n_spans,
+                                   int32_t* labels, int cus, hipStream_t stream);
+// top_labels[d][0 .. k) = -1 and top_scores (nullable) [d][0 .. k) = 0.0 where host[d] is set
+hipError_t launch_utf8_topk_labels(const uint8_t* host, int64_t n_docs, int32_t k, int32_t* top_labels,
+                                   double* top_scores, int cus, hipStream_t stream);
+
 }  // namespace ldgpu

@@ -196,9 +196,136 @@ __global__ void utf8_label_kernel(const uint8_t* host, int64_t n, int32_t* label
         if (host[d]) labels[d] = -1;
 }
 
+// ---- spans of UTF-8 documents (include/ldgpu.h UTF-8: top-k, spans, segments)
+// len[d]: in, document d's units (pass 1; 0 for an ill-formed one); out, its
+// spans.  units (nullable) [n_docs]: the unit count, -1 for an ill-formed one.
+__global__ __launch_bounds__(256) void utf8_span_count_kernel(int64_t* len, const uint8_t* host, int64_t n_docs,
+                                                              int32_t width, int32_t stride, int64_t* units) {
+    const int64_t n = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; d < n_docs; d += n) {
+        const int64_t u = len[d];
+        if (units) units[d] = host[d] ? -1 : u;
+        len[d] = u <= width ? 1 : 1 + (u - width + stride - 1) / stride;
+    }
+}
+
+// Every span's start as a byte index into its document: span j of a document
+// starts at unit j stride, and its start is the position of the lead byte that
+// unit belongs to (both units of a 4-byte lead belong to it).  A kernel of its
+// own in the shape of the write pass -- one wave per well-formed document, a
+// dword per lane and step, the same masks and the same five-ballot unit rank
+// -- which needs the leads alone: a lead's length says how many units it
+// gives, so no follower is looked at and nothing is decoded.
+//
+// The wave keeps the next span start (unit nu = nj stride) across the steps:
+// a step holding the units [o, o + total) has a start iff nu < o + total, a
+// wave-uniform test, and only such a step divides (a lane's unit minus the
+// step's first start, below 2^9, by stride); with stride beyond a step's units
+// most steps skip all of it.  The loop ends with the document's last span:
+// the spans' starts lie below u - width + stride, so the tail is not read.
+__global__ __launch_bounds__(kUtf8Waves * 64) void utf8_starts_kernel(const Utf8StartParams p) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t* words = reinterpret_cast<const uint32_t*>(p.utf8);
+    const int64_t nw = (int64_t)gridDim.x * kUtf8Waves;
+    const uint32_t stride = (uint32_t)p.stride;
+    for (int64_t d = (int64_t)blockIdx.x * kUtf8Waves + (threadIdx.x >> 6); d < p.n_docs; d += nw) {
+        if (p.host[d]) continue;
+        const int64_t b = p.offsets[d], e = p.offsets[d + 1];
+        const int64_t s0 = p.span_offsets[d];
+        if (s0 < 0 || s0 >= p.n_spans) continue;
+        // the document's spans, cut to the array
+        const int64_t s1 = p.span_offsets[d + 1];
+        const int64_t ns = (s1 < p.n_spans ? s1 : p.n_spans) - s0;
+        int64_t o = 0;           // units before this step
+        int64_t nu = 0, nj = 0;  // the next span start: unit nu of span nj
+        int64_t dw = (b >> 2) + lane;
+        uint32_t cur = utf8_dword(words, dw, e);
+        for (int64_t a = b & ~(int64_t)3; a < e && nj < ns; a += kUtf8Step, dw += 64) {
+            const uint32_t ahead = utf8_dword(words, dw + 64, e);
+            const int64_t pos0 = a + 4 * lane;
+            int n[4];
+            int cnt = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int64_t pos = pos0 + j;
+                n[j] = pos >= b && pos < e ? utf8_lead_len((cur >> (8 * j)) & 0xFFu) : 0;
+                cnt += n[j] == 4 ? 2 : (n[j] >= 1 ? 1 : 0);
+            }
+            uint32_t rank = 0, total = 0;
+#pragma unroll
+            for (int k = 1; k <= 5; ++k) {
+                const uint64_t m = __ballot(cnt >= k);
+                rank += __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                total += (uint32_t)__popcll(m);
+            }
+            const int64_t end = o + (int64_t)total;
+            if (nu < end) {
+                const uint32_t first = (uint32_t)(nu - o);  // the step's first start, in units of the step
+                uint32_t r = rank;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int units = n[j] == 4 ? 2 : (n[j] >= 1 ? 1 : 0);
+#pragma unroll
+                    for (int t = 0; t < 2; ++t) {
+                        const uint32_t ru = r + (uint32_t)t;
+                        if (t < units && ru >= first) {
+                            const uint32_t q = (ru - first) / stride;
+                            if (q * stride == ru - first && nj + (int64_t)q < ns)
+                                p.starts[s0 + nj + (int64_t)q] = pos0 + j - b;
+                        }
+                    }
+                    r += (uint32_t)units;
+                }
+                const int64_t k = (int64_t)((uint32_t)(end - 1 - nu) / stride) + 1;  // the step's starts
+                nj += k;
+                nu += k * (int64_t)stride;
+            }
+            o = end;
+            cur = ahead;
+        }
+    }
+}
+
+// start 0 where no lead writes one: span 0 of an empty or ill-formed document,
+// and the entries at and beyond span_offsets[n_docs]
+__global__ __launch_bounds__(256) void utf8_start_fill_kernel(const Utf8StartParams p) {
+    const int64_t n = (int64_t)gridDim.x * blockDim.x, t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (int64_t d = t; d < p.n_docs; d += n) {
+        const int64_t s = p.span_offsets[d];
+        if ((p.host[d] || p.offsets[d + 1] <= p.offsets[d]) && s >= 0 && s < p.n_spans) p.starts[s] = 0;
+    }
+    const int64_t total = p.span_offsets[p.n_docs];
+    for (int64_t g = (total > 0 ? total : 0) + t; g < p.n_spans; g += n) p.starts[g] = 0;
+}
+
+__global__ __launch_bounds__(256) void utf8_span_label_kernel(const uint8_t* host, const int64_t* span_offsets,
+                                                              int64_t n_docs, int64_t n_spans, int32_t* labels) {
+    const int64_t n = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; d < n_docs; d += n) {
+        const int64_t s = span_offsets[d];
+        if (host[d] && s >= 0 && s < n_spans) labels[s] = -1;
+    }
+}
+
+__global__ __launch_bounds__(256) void utf8_topk_label_kernel(const uint8_t* host, int64_t n_docs, int32_t k,
+                                                              int32_t* top_labels, double* top_scores) {
+    const int64_t n = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; d < n_docs; d += n) {
+        if (!host[d]) continue;
+        for (int32_t i = 0; i < k; ++i) {
+            top_labels[d * k + i] = -1;
+            if (top_scores) top_scores[d * k + i] = 0.0;
+        }
+    }
+}
+
 int utf8_grid(int64_t n, int cus) {
     const int64_t want = (n + kUtf8Waves - 1) / kUtf8Waves;
     return (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)cus * 8));
+}
+
+int utf8_flat_grid(int64_t n, int cus) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, (int64_t)cus * 8));
 }
 
 }  // namespace
@@ -224,6 +351,50 @@ hipError_t launch_utf8_labels(const uint8_t* host, int64_t n_docs, int32_t* labe
     if (n_docs <= 0) return hipSuccess;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n_docs + 255) / 256, (int64_t)cus * 8));
     hipLaunchKernelGGL(utf8_label_kernel, dim3(grid), dim3(256), 0, stream, host, n_docs, labels);
+    return hipGetLastError();
+}
+
+hipError_t launch_utf8_span_offsets(const Utf8Params& p, int32_t width, int32_t stride, int64_t* len_tmp,
+                                    int64_t* span_offsets, int64_t* units, void* scan_tmp, size_t* scan_bytes,
+                                    int cus, hipStream_t stream) {
+    if (!scan_tmp)
+        return hipcub::DeviceScan::ExclusiveSum(nullptr, *scan_bytes, len_tmp, span_offsets, (int)(p.n_docs + 1), stream);
+    if (p.n_docs <= 0) return hipMemsetAsync(span_offsets, 0, sizeof(int64_t), stream);
+    hipLaunchKernelGGL(utf8_len_kernel, dim3(utf8_grid(p.n_docs, cus)), dim3(kUtf8Waves * 64), 0, stream, p, len_tmp);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(utf8_span_count_kernel, dim3(utf8_flat_grid(p.n_docs, cus)), dim3(256), 0, stream, len_tmp,
+                       p.host, p.n_docs, width, stride, units);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return hipcub::DeviceScan::ExclusiveSum(scan_tmp, *scan_bytes, len_tmp, span_offsets, (int)(p.n_docs + 1), stream);
+}
+
+hipError_t launch_utf8_starts(const Utf8StartParams& p, int cus, hipStream_t stream) {
+    if (!p.starts || p.n_spans <= 0) return hipSuccess;
+    if (p.n_docs > 0) {
+        hipLaunchKernelGGL(utf8_starts_kernel, dim3(utf8_grid(p.n_docs, cus)), dim3(kUtf8Waves * 64), 0, stream, p);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(utf8_start_fill_kernel, dim3(utf8_flat_grid(std::max(p.n_docs, p.n_spans), cus)), dim3(256), 0,
+                       stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_utf8_span_labels(const uint8_t* host, const int64_t* span_offsets, int64_t n_docs, int64_t n_spans,
+                                   int32_t* labels, int cus, hipStream_t stream) {
+    if (n_docs <= 0 || n_spans <= 0) return hipSuccess;
+    hipLaunchKernelGGL(utf8_span_label_kernel, dim3(utf8_flat_grid(n_docs, cus)), dim3(256), 0, stream, host,
+                       span_offsets, n_docs, n_spans, labels);
+    return hipGetLastError();
+}
+
+hipError_t launch_utf8_topk_labels(const uint8_t* host, int64_t n_docs, int32_t k, int32_t* top_labels,
+                                   double* top_scores, int cus, hipStream_t stream) {
+    if (n_docs <= 0) return hipSuccess;
+    hipLaunchKernelGGL(utf8_topk_label_kernel, dim3(utf8_flat_grid(n_docs, cus)), dim3(256), 0, stream, host, n_docs, k,
+                       top_labels, top_scores);
     return hipGetLastError();
 }
 

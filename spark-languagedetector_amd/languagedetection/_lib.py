@@ -75,6 +75,17 @@ SIGNATURES = [
     ("ldgpu_score_segments", ctypes.c_int, [_p, _p, _p, _i64, _i32, _i32, ctypes.c_double, _p]),
     ("ldgpu_score_segments_device", ctypes.c_int,
      [_p, _p, _i64, _p, _i64, _i32, _i32, ctypes.c_double, _p, _i64, _p, _p]),
+    # include/ldgpu.h UTF-8: top-k, spans, segments (letters and underscores only: listed here)
+    ("ldgpu_span_offsets_utf", ctypes.c_int, [_p, _p, _p, _i64, _i32, _i32, _p, _p]),
+    ("ldgpu_span_offsets_utf_device", ctypes.c_int, [_p, _p, _p, _i64, _i32, _i32, _p, _p, _p]),
+    ("ldgpu_score_topk_utf", ctypes.c_int, [_p, _p, _p, _i64, _i32, _p, _p]),
+    ("ldgpu_score_topk_utf_device", ctypes.c_int, [_p, _p, _i64, _p, _i64, _i32, _p, _p, _p]),
+    ("ldgpu_score_spans_utf", ctypes.c_int, [_p, _p, _p, _i64, _i32, _i32, _p, _p, _p, _p]),
+    ("ldgpu_score_spans_utf_device", ctypes.c_int,
+     [_p, _p, _i64, _p, _i64, _i32, _i32, _p, _i64, _p, _p, _p, _p]),
+    ("ldgpu_score_segments_utf", ctypes.c_int, [_p, _p, _p, _i64, _i32, _i32, ctypes.c_double, _p, _p, _p]),
+    ("ldgpu_score_segments_utf_device", ctypes.c_int,
+     [_p, _p, _i64, _p, _i64, _i32, _i32, ctypes.c_double, _p, _i64, _p, _p, _p]),
     ("ldgpu_counts_create", ctypes.c_int, [_p, _i32, _p, _i32, _i64, _pp]),
     ("ldgpu_counts_destroy", ctypes.c_int, [_p]),
     ("ldgpu_counts_langs", ctypes.c_int, [_p, _pi32]),

@@ -156,15 +156,7 @@ class LanguageDetectorModel(_Params):
         restatement is."""
         if errors not in ("replace", "strict"):
             raise ValueError(f"errors must be \"replace\" or \"strict\", not {errors!r}")
-        if isinstance(docs, tuple) and len(docs) == 2 and isinstance(docs[0], np.ndarray):
-            data = np.ascontiguousarray(docs[0], dtype=np.uint8)
-            offsets = np.ascontiguousarray(docs[1], dtype=np.int64)
-        else:
-            docs = list(docs)
-            for d in docs:
-                if d is None:
-                    raise NullPointerException("text is null")
-            data, offsets = utf8.pack_utf8(docs)
+        data, offsets = self._packed_utf8(docs)
         labels, scores = self.device_model().score_utf8(data, offsets, want_scores)
         bad = np.flatnonzero(labels < 0)
         if len(bad):
@@ -177,6 +169,137 @@ class LanguageDetectorModel(_Params):
             if want_scores:
                 scores[bad] = s2
         return labels, scores
+
+    @staticmethod
+    def _packed_utf8(docs) -> Tuple[np.ndarray, np.ndarray]:
+        """`docs` (a sequence of bytes, or a packed (data, offsets) pair) as
+        (data uint8, offsets int64[n + 1])."""
+        if isinstance(docs, tuple) and len(docs) == 2 and isinstance(docs[0], np.ndarray):
+            return np.ascontiguousarray(docs[0], dtype=np.uint8), np.ascontiguousarray(docs[1], dtype=np.int64)
+        docs = list(docs)
+        for d in docs:
+            if d is None:
+                raise NullPointerException("text is null")
+        return utf8.pack_utf8(docs)
+
+    def _utf8_frame(self, dataset, new_cols):
+        """(the frame, its inputCol as a list) for the transform*Utf8 calls:
+        the column checks of transformUtf8, for the output columns `new_cols`."""
+        import pandas as pd
+        df = dataset if isinstance(dataset, pd.DataFrame) else pd.DataFrame(dataset)
+        if self.getInputCol() not in df.columns:
+            raise ValueError(f"Field \"{self.getInputCol()}\" does not exist.")
+        col = list(df[self.getInputCol()])
+        if not all(v is None or isinstance(v, (bytes, bytearray)) for v in col):
+            raise ValueError("requirement failed: Input type must be BinaryType (UTF-8 bytes).")
+        for c in new_cols:
+            if c in df.columns:
+                raise ValueError(f"requirement failed: Column {c} already exists.")
+        return df, col
+
+    # The other output forms over UTF-8 documents.  Runs come in the caller's
+    # own coordinates: coords="bytes" indexes the document's UTF-8 bytes
+    # (utf8.byte_runs over the starts the device computed while decoding),
+    # coords="units" the UTF-16 units of the decoded text, as predict_spans.
+    def predict_topk_utf8(self, docs, k: int, errors: str = "replace") -> Tuple[List[List[str]], np.ndarray]:
+        """predict_topk over UTF-8 documents (`docs` as in predict_indices_utf8);
+        an ill-formed document is handled by `errors` as there."""
+        if errors not in ("replace", "strict"):
+            raise ValueError(f"errors must be \"replace\" or \"strict\", not {errors!r}")
+        data, offsets = self._packed_utf8(docs)
+        labels, scores = self.device_model().score_topk_utf8(data, offsets, k, want_scores=True)
+        bad = np.flatnonzero(labels[:, 0] < 0) if labels.size else np.zeros(0, dtype=np.int64)
+        langs = [[self.supportedLanguages[i] for i in row] if row[0] >= 0 else None for row in labels]
+        if len(bad):
+            raw = [data[int(offsets[i]):int(offsets[i + 1])].tobytes() for i in bad]
+            if errors == "strict":
+                raw[0].decode("utf-8")  # raises UnicodeDecodeError
+                raise AssertionError(f"document {int(bad[0])}: flagged ill-formed, but the codec decodes it")
+            l2, s2 = self.predict_topk([r.decode("utf-8", "replace") for r in raw], k)
+            for i, row in zip(bad, l2):
+                langs[int(i)] = row
+            scores[bad] = s2
+        return langs, scores
+
+    def _utf8_runs(self, docs, width: int, stride: int, penalty, coords: str, errors: str):
+        if coords not in ("bytes", "units"):
+            raise ValueError(f"coords must be \"bytes\" or \"units\", not {coords!r}")
+        if errors not in ("strict", "skip"):
+            raise ValueError(f"errors must be \"strict\" or \"skip\", not {errors!r}")
+        data, offsets = self._packed_utf8(docs)
+        dev = self.device_model()
+        soff, units = dev.span_offsets_utf8(data, offsets, width, stride)
+        want_starts = coords == "bytes"
+        if penalty is None:
+            labels, _, starts, _ = dev.score_spans_utf8(data, offsets, width, stride, want_starts=want_starts,
+                                                        span_offsets=soff)
+        else:
+            labels, starts, _ = dev.score_segments_utf8(data, offsets, width, stride, penalty,
+                                                        want_starts=want_starts, span_offsets=soff)
+        out = []
+        for d in range(len(offsets) - 1):
+            a, b = int(soff[d]), int(soff[d + 1])
+            if units[d] < 0:
+                if errors == "strict":
+                    data[int(offsets[d]):int(offsets[d + 1])].tobytes().decode("utf-8")  # raises UnicodeDecodeError
+                    raise AssertionError(f"document {d}: flagged ill-formed, but the codec decodes it")
+                out.append(None)
+                continue
+            if coords == "units":
+                r = spans.runs(int(units[d]), labels[a:b], width, stride)
+            else:
+                r = utf8.byte_runs(starts[a:b], int(offsets[d + 1] - offsets[d]), labels[a:b])
+            out.append([(x, y, self.supportedLanguages[lab]) for x, y, lab in r])
+        return out
+
+    def predict_spans_utf8(self, docs, width: int, stride: int, coords: str = "bytes", errors: str = "strict"):
+        """predict_spans over UTF-8 documents (`docs` as in
+        predict_indices_utf8; width and stride in UTF-16 units).  coords:
+          "units"  the runs of predict_spans on the decoded texts;
+          "bytes"  (start, end, language) index the document's own bytes
+                   (utf8.byte_runs): every run is whole characters.
+        An ill-formed document raises UnicodeDecodeError under errors="strict"
+        and yields None under "skip"; a replacement decode would give
+        coordinates into a text the caller does not hold, so there is no
+        "replace" here."""
+        return self._utf8_runs(docs, width, stride, None, coords, errors)
+
+    def predict_segments_utf8(self, docs, width: int, stride: int, penalty: float, coords: str = "bytes",
+                              errors: str = "strict"):
+        """predict_segments over UTF-8 documents: coords and errors as in
+        predict_spans_utf8."""
+        return self._utf8_runs(docs, width, stride, float(penalty), coords, errors)
+
+    def transformTopKUtf8(self, dataset, k: int, candidatesCol: str = "lang_candidates",
+                          scoresCol: str = "lang_scores", errors: str = "replace"):
+        """transformTopK for an inputCol of bytes (UTF-8)."""
+        import pandas as pd
+        df, col = self._utf8_frame(dataset, (candidatesCol, scoresCol))
+        langs, scores = self.predict_topk_utf8(col, k, errors=errors)
+        out = df.copy()
+        out[candidatesCol] = pd.Series(langs, index=out.index, dtype=object)
+        out[scoresCol] = pd.Series([row.tolist() for row in scores], index=out.index, dtype=object)
+        return out
+
+    def transformSpansUtf8(self, dataset, width: int, stride: int, outputCol: str = "langSpans",
+                           coords: str = "bytes", errors: str = "strict"):
+        """transformSpans for an inputCol of bytes (UTF-8)."""
+        import pandas as pd
+        df, col = self._utf8_frame(dataset, (outputCol,))
+        found = self.predict_spans_utf8(col, width, stride, coords=coords, errors=errors)
+        out = df.copy()
+        out[outputCol] = pd.Series(found, index=out.index, dtype=object)
+        return out
+
+    def transformSegmentsUtf8(self, dataset, width: int, stride: int, penalty: float,
+                              outputCol: str = "langSegments", coords: str = "bytes", errors: str = "strict"):
+        """transformSegments for an inputCol of bytes (UTF-8)."""
+        import pandas as pd
+        df, col = self._utf8_frame(dataset, (outputCol,))
+        found = self.predict_segments_utf8(col, width, stride, penalty, coords=coords, errors=errors)
+        out = df.copy()
+        out[outputCol] = pd.Series(found, index=out.index, dtype=object)
+        return out
 
     def transformUtf8(self, dataset, errors: str = "replace"):
         """transform for an inputCol of bytes (UTF-8): appends outputCol = the

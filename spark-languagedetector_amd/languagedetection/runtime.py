@@ -289,6 +289,143 @@ class DeviceModel(_Owner):
                                                          ctypes.c_void_p(st) if st else None))
 
 
+    # Top-k, spans and segments of UTF-8 documents (an addition; the rule:
+    # languagedetection.utf8)
+    def span_offsets_utf8(self, data: np.ndarray, offsets: np.ndarray, width: int, stride: int
+                          ) -> Tuple[np.ndarray, np.ndarray]:
+        """Host buffers of UTF-8 documents -> (span_offsets int64[n_docs + 1],
+        units int64[n_docs]: the document's UTF-16 unit count, -1 = ill-formed),
+        from the device decoder's length pass (ldgpu_span_offsets_utf)."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = len(offsets) - 1
+        soff = np.zeros(max(n, 0) + 1, dtype=np.int64)
+        units = np.zeros(max(n, 1), dtype=np.int64)
+        self._check(self.lib.ldgpu_span_offsets_utf(self.ctx, _ptr(data), _ptr(offsets), n, int(width), int(stride),
+                                                    _ptr(soff), _ptr(units)))
+        return soff, units[:max(n, 0)]
+
+    def span_offsets_utf8_device(self, d_utf8: int, d_offsets: int, n_docs: int, width: int, stride: int,
+                                 d_span_offsets: int, d_units: int = 0, stream: Optional[int] = None) -> None:
+        """Device pointers -> d_span_offsets int64[n_docs + 1] (and d_units
+        int64[n_docs]) in place, async on `stream` as score_device
+        (ldgpu_span_offsets_utf_device)."""
+        st = self.stream() if stream is None else stream
+        self._check(self.lib.ldgpu_span_offsets_utf_device(self.ctx, ctypes.c_void_p(d_utf8),
+                                                           ctypes.c_void_p(d_offsets), n_docs, int(width), int(stride),
+                                                           ctypes.c_void_p(d_span_offsets),
+                                                           ctypes.c_void_p(d_units) if d_units else None,
+                                                           ctypes.c_void_p(st) if st else None))
+
+    def score_topk_utf8(self, data: np.ndarray, offsets: np.ndarray, k: int, want_scores: bool = True,
+                        out_labels: Optional[np.ndarray] = None, out_scores: Optional[np.ndarray] = None
+                        ) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+        """score_topk over host buffers of UTF-8 documents, decoded on the
+        device (ldgpu_score_topk_utf); an ill-formed document's row is -1 in
+        every label and 0.0 in every score."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n, k = max(len(offsets) - 1, 0), int(k)
+        shape = (n, max(k, 0))
+        labels = np.zeros(shape, dtype=np.int32) if out_labels is None else out_labels
+        scores = (np.zeros(shape, dtype=np.float64) if out_scores is None else out_scores) if want_scores else None
+        assert labels.dtype == np.int32 and labels.shape == shape and labels.flags.c_contiguous
+        assert scores is None or (scores.dtype == np.float64 and scores.shape == shape and scores.flags.c_contiguous)
+        self._check(self.lib.ldgpu_score_topk_utf(self.h, _ptr(data), _ptr(offsets), len(offsets) - 1, k, _ptr(labels),
+                                                  _ptr(scores)))
+        return labels, scores
+
+    def score_topk_utf8_device(self, d_utf8: int, n_bytes: int, d_offsets: int, n_docs: int, k: int,
+                               d_top_labels: int, d_top_scores: int = 0, stream: Optional[int] = None) -> None:
+        """Device pointers to UTF-8 documents -> the [n_docs, k] labels (and
+        scores) in place, async on `stream` (ldgpu_score_topk_utf_device)."""
+        st = self.stream() if stream is None else stream
+        self._check(self.lib.ldgpu_score_topk_utf_device(self.h, ctypes.c_void_p(d_utf8), n_bytes,
+                                                         ctypes.c_void_p(d_offsets), n_docs, int(k),
+                                                         ctypes.c_void_p(d_top_labels),
+                                                         ctypes.c_void_p(d_top_scores) if d_top_scores else None,
+                                                         ctypes.c_void_p(st) if st else None))
+
+    def score_spans_utf8(self, data: np.ndarray, offsets: np.ndarray, width: int, stride: int,
+                         want_scores: bool = False, want_starts: bool = True,
+                         span_offsets: Optional[np.ndarray] = None, out_labels: Optional[np.ndarray] = None,
+                         out_scores: Optional[np.ndarray] = None, out_starts: Optional[np.ndarray] = None
+                         ) -> Tuple[np.ndarray, Optional[np.ndarray], Optional[np.ndarray], np.ndarray]:
+        """Host buffers of UTF-8 documents -> (labels int32[n_spans], scores
+        fp64[n_spans, L] or None, starts int64[n_spans] or None, span_offsets
+        int64[n_docs + 1]): score_spans of the documents' SCORE encoding, plus
+        every span's start as a byte index into its document; an ill-formed
+        document's single span gets -1 (ldgpu_score_spans_utf).  `span_offsets`
+        is span_offsets_utf8's output when the caller has it already; the
+        `out_*` arrays (e.g. PinnedArray arrays) receive the results."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        soff = (self.span_offsets_utf8(data, offsets, width, stride)[0] if span_offsets is None
+                else np.ascontiguousarray(span_offsets, dtype=np.int64))
+        n = int(soff[-1])
+        labels = np.zeros(n, dtype=np.int32) if out_labels is None else out_labels
+        scores = (np.zeros((n, self.L), dtype=np.float64) if out_scores is None else out_scores) if want_scores else None
+        starts = (np.zeros(n, dtype=np.int64) if out_starts is None else out_starts) if want_starts else None
+        assert labels.dtype == np.int32 and labels.shape == (n,) and labels.flags.c_contiguous
+        assert scores is None or (scores.dtype == np.float64 and scores.shape == (n, self.L)
+                                  and scores.flags.c_contiguous)
+        assert starts is None or (starts.dtype == np.int64 and starts.shape == (n,) and starts.flags.c_contiguous)
+        self._check(self.lib.ldgpu_score_spans_utf(self.h, _ptr(data), _ptr(offsets), len(offsets) - 1, int(width),
+                                                   int(stride), _ptr(soff), _ptr(labels), _ptr(scores), _ptr(starts)))
+        return labels, scores, starts, soff
+
+    def score_spans_utf8_device(self, d_utf8: int, n_bytes: int, d_offsets: int, n_docs: int, width: int, stride: int,
+                                d_span_offsets: int, n_spans: int, d_labels: int, d_scores: int = 0,
+                                d_starts: int = 0, stream: Optional[int] = None) -> None:
+        """Device pointers to UTF-8 documents -> the [n_spans] labels (and
+        [n_spans, L] scores, [n_spans] starts) in place, async on `stream`
+        (ldgpu_score_spans_utf_device)."""
+        st = self.stream() if stream is None else stream
+        self._check(self.lib.ldgpu_score_spans_utf_device(self.h, ctypes.c_void_p(d_utf8), n_bytes,
+                                                          ctypes.c_void_p(d_offsets), n_docs, int(width), int(stride),
+                                                          ctypes.c_void_p(d_span_offsets), n_spans,
+                                                          ctypes.c_void_p(d_labels),
+                                                          ctypes.c_void_p(d_scores) if d_scores else None,
+                                                          ctypes.c_void_p(d_starts) if d_starts else None,
+                                                          ctypes.c_void_p(st) if st else None))
+
+    def score_segments_utf8(self, data: np.ndarray, offsets: np.ndarray, width: int, stride: int, penalty: float,
+                            want_starts: bool = True, span_offsets: Optional[np.ndarray] = None,
+                            out_labels: Optional[np.ndarray] = None, out_starts: Optional[np.ndarray] = None
+                            ) -> Tuple[np.ndarray, Optional[np.ndarray], np.ndarray]:
+        """Host buffers of UTF-8 documents -> (labels int32[n_spans], starts
+        int64[n_spans] or None, span_offsets int64[n_docs + 1]): score_segments
+        of the documents' SCORE encoding with the spans' byte starts; an
+        ill-formed document's single span gets -1 (ldgpu_score_segments_utf)."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        soff = (self.span_offsets_utf8(data, offsets, width, stride)[0] if span_offsets is None
+                else np.ascontiguousarray(span_offsets, dtype=np.int64))
+        n = int(soff[-1])
+        labels = np.zeros(n, dtype=np.int32) if out_labels is None else out_labels
+        starts = (np.zeros(n, dtype=np.int64) if out_starts is None else out_starts) if want_starts else None
+        assert labels.dtype == np.int32 and labels.shape == (n,) and labels.flags.c_contiguous
+        assert starts is None or (starts.dtype == np.int64 and starts.shape == (n,) and starts.flags.c_contiguous)
+        self._check(self.lib.ldgpu_score_segments_utf(self.h, _ptr(data), _ptr(offsets), len(offsets) - 1, int(width),
+                                                      int(stride), float(penalty), _ptr(soff), _ptr(labels),
+                                                      _ptr(starts)))
+        return labels, starts, soff
+
+    def score_segments_utf8_device(self, d_utf8: int, n_bytes: int, d_offsets: int, n_docs: int, width: int,
+                                   stride: int, penalty: float, d_span_offsets: int, n_spans: int, d_labels: int,
+                                   d_starts: int = 0, stream: Optional[int] = None) -> None:
+        """Device pointers to UTF-8 documents -> the [n_spans] smoothed labels
+        (and starts) in place, async on `stream` (ldgpu_score_segments_utf_device)."""
+        st = self.stream() if stream is None else stream
+        self._check(self.lib.ldgpu_score_segments_utf_device(self.h, ctypes.c_void_p(d_utf8), n_bytes,
+                                                             ctypes.c_void_p(d_offsets), n_docs, int(width),
+                                                             int(stride), float(penalty),
+                                                             ctypes.c_void_p(d_span_offsets), n_spans,
+                                                             ctypes.c_void_p(d_labels),
+                                                             ctypes.c_void_p(d_starts) if d_starts else None,
+                                                             ctypes.c_void_p(st) if st else None))
+
+
 class DeviceCounts(_Owner):
     """A (gram, language) -> count table on one GPU (computeGrams + reduceGrams)."""
 

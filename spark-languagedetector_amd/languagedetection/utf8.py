@@ -16,6 +16,45 @@ the codec is what this module is tested against, so nothing here calls it.
 
 A code point below 0x10000 gives one UTF-16 unit, a larger one a surrogate
 pair; an ill-formed document is not decoded (host flag 1, empty output).
+
+Spans of UTF-8 documents (ldgpu_span_offsets_utf, ldgpu_score_spans_utf,
+ldgpu_score_segments_utf, ldgpu_score_topk_utf and their _device forms;
+``span_geometry`` and ``byte_runs`` below are their checker).  The rule:
+
+  - `width` and `stride` count UTF-16 units (= SCORE bytes), exactly as in
+    ldgpu_score_spans.
+  - A document's spans are those of ldgpu_span_offsets applied to its unit
+    count u: one span if u <= width, otherwise 1 + ceil((u - width) / stride).
+  - Well-formedness is ldgpu_utf8_decode's rule (Unicode Table 3-7).  An
+    ill-formed document counts as u = 0: it has one empty span.
+  - units[d] is u for a well-formed document and -1 for an ill-formed one.
+  - start[i], for span j of document d, is an int64 byte index relative to
+    the document's first byte: the index of the lead byte of the character
+    that unit j * stride belongs to.  If unit j * stride is the low surrogate
+    of a 4-byte character (the boundary splits the pair), it is that
+    character's lead byte.  A character's bytes therefore always belong to
+    one run, the one starting at or before its first unit.  At stride == 1
+    both units of a pair give the same start.  Span 0 of every document has
+    start 0; this includes an empty document's single span and an ill-formed
+    document's single span.  Starts are non-decreasing within a document.
+    Every start is < len for a non-empty well-formed document.
+  - Labels and score rows of a well-formed document's spans are bit for bit
+    those of ldgpu_score_spans, ldgpu_score_segments or ldgpu_score_topk on
+    its SCORE encoding, on every model layout.
+  - For an ill-formed document: its single span gets label -1 and the empty
+    document's score row; the top-k form gives -1 in all k label entries and
+    0.0 in the scores; the segment form gives -1.
+  - ``byte_runs`` turns span labels into runs in bytes.  Span j owns bytes
+    [start[j], start[j+1]), the last span up to the document's byte length.
+    Consecutive spans of one label merge.  Empty runs are dropped.  This is
+    the byte twin of ``spans.runs``.
+
+The byte runs carry the labels of ``spans.runs`` in the same order, except
+where a unit run holds no whole character.  That happens where a span boundary
+splits a surrogate pair: the character's bytes go, whole, to the span that
+starts at its low surrogate.  A span that is nothing but such a pair's high
+surrogate (stride 1) then owns no byte: its start equals the next span's, its
+byte run is empty and is dropped, while ``spans.runs`` keeps a run of one unit.
 """
 from __future__ import annotations
 
@@ -64,6 +103,60 @@ def pack_utf8(docs: Sequence[bytes]) -> Tuple[np.ndarray, np.ndarray]:
     to a multiple of 4 bytes (+4), as encoding.pack does."""
     from .encoding import pack
     return pack([bytes(d) for d in docs])
+
+
+def span_geometry(data, offsets, width: int, stride: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(span_offsets int64[n + 1], units int64[n], starts int64[n_spans]) of
+    the documents data[offsets[d]:offsets[d + 1]] by the rule above: what
+    ldgpu_span_offsets_utf and the `starts` of ldgpu_score_spans_utf give."""
+    from .spans import check
+    check(width, stride)
+    data = np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else np.asarray(data, dtype=np.uint8)
+    offsets = np.asarray(offsets, dtype=np.int64)
+    n_docs = len(offsets) - 1
+    if n_docs <= 0:
+        return np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+    _, unit_off, host = decode(data, offsets, low_bytes=True)
+    u = np.diff(unit_off)
+    units = np.where(host != 0, -1, u)
+    counts = np.where(u <= width, 1, 1 + -(-(u - width) // stride))
+    span_offsets = np.zeros(n_docs + 1, dtype=np.int64)
+    np.cumsum(counts, out=span_offsets[1:])
+    starts = np.zeros(int(span_offsets[-1]), dtype=np.int64)
+    # the leads of the well-formed documents: byte position, document, first unit
+    b0, b1 = int(offsets[0]), int(offsets[-1])
+    c = data[b0:b1].astype(np.int64)
+    pos = np.arange(len(c), dtype=np.int64) + b0
+    doc = np.searchsorted(offsets, pos, side="right") - 1
+    lead = (_LEN[c] >= 1) & (host[doc] == 0) if len(c) else np.zeros(0, dtype=bool)
+    pos, doc, two = pos[lead], doc[lead], _LEN[c[lead]] == 4
+    n_units = np.where(two, 2, 1)
+    rank = np.cumsum(n_units) - n_units - unit_off[doc]      # the lead's first unit within its document
+    for t, has in ((0, np.ones(len(pos), dtype=bool)), (1, two)):
+        r = rank + t
+        at = has & (r % stride == 0) & (r // stride < counts[doc])
+        starts[span_offsets[doc[at]] + r[at] // stride] = pos[at] - offsets[doc[at]]
+    return span_offsets, units, starts
+
+
+def byte_runs(starts_d, n_bytes_d: int, labels_d) -> list:
+    """[(start, end, label)] in bytes of one document of `n_bytes_d` bytes from
+    its spans' starts and labels: span j owns [starts_d[j], starts_d[j + 1]),
+    the last span up to n_bytes_d; consecutive spans of one label merge, empty
+    runs are dropped (the byte twin of spans.runs)."""
+    if len(starts_d) != len(labels_d):
+        raise ValueError(f"{len(labels_d)} labels for {len(starts_d)} span starts")
+    n = len(starts_d)
+    out = []
+    for j in range(n):
+        a, b, lab = int(starts_d[j]), (int(n_bytes_d) if j == n - 1 else int(starts_d[j + 1])), int(labels_d[j])
+        if b <= a:
+            continue
+        if out and out[-1][2] == lab:
+            out[-1] = (out[-1][0], b, lab)
+        else:
+            out.append((a, b, lab))
+    return out
 
 
 def decode(data, offsets, low_bytes: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
