@@ -2223,31 +2223,42 @@ int check_row_error(ldgpu_model* m, int32_t* d_err, hipStream_t st) {
     return LDGPU_OK;
 }
 
-// The start of a device-pointer scoring call: the checks the three entry
-// points share, in their order -- the model, n_docs, the call's own arguments
-// (`own`, run once the model is known), a missing pointer (`null_ptr`, worked
-// out by the caller), d_bytes' alignment -- then the model's device made current.
+// The start of a device-pointer scoring call: the checks the entry points
+// share, in their order -- the model, n_docs, the call's own arguments (`own`,
+// run once the model is known), a missing pointer (with an item -- a document,
+// or a span -- at all: one of `need`, or d_bytes when there are bytes),
+// d_bytes' alignment -- then the model's device made current.
 template <class Own>
-int device_call_begin(const ldgpu_model* m, int64_t n_docs, const void* d_bytes, bool null_ptr, Own own) {
+int device_call_begin(const ldgpu_model* m, int64_t n_docs, int64_t n_items, const void* d_bytes, int64_t n_bytes,
+                      std::initializer_list<const void*> need, Own own) {
     if (!m) return fail(LDGPU_EINVAL, "model is NULL");
     if (n_docs < 0) return fail(LDGPU_EINVAL, "n_docs < 0");
     if (int rc = own()) return rc;
-    if (null_ptr) return fail(LDGPU_EINVAL, "device pointer is NULL");
+    bool null_ptr = n_bytes > 0 && !d_bytes;
+    for (const void* p : need) null_ptr = null_ptr || !p;
+    if (n_items > 0 && null_ptr) return fail(LDGPU_EINVAL, "device pointer is NULL");
     if (((uintptr_t)d_bytes & 3) != 0) return fail(LDGPU_EINVAL, "d_bytes must be 4-byte aligned");
     HIP_TRY(hipSetDevice(m->ctx->device));
     return LDGPU_OK;
 }
 const auto no_own_checks = [] { return (int)LDGPU_OK; };
+
+// ... and its end, once the call's launches are queued on st
+int device_call_end(ldgpu_model* m, hipStream_t st) {
+    if (int rc = check_row_error(m, m->d_err, st)) return rc;
+    return ok();
+}
+
+size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
 }  // namespace
 
 extern "C" int ldgpu_score_device(ldgpu_model* m, const uint8_t* d_bytes, int64_t n_bytes, const int64_t* d_offsets,
                                   int64_t n_docs, int32_t* d_labels, double* d_scores, void* stream) {
-    const bool null_ptr = n_docs > 0 && (!d_offsets || !d_labels || (n_bytes > 0 && !d_bytes));
-    if (int rc = device_call_begin(m, n_docs, d_bytes, null_ptr, no_own_checks)) return rc;
+    if (int rc = device_call_begin(m, n_docs, n_docs, d_bytes, n_bytes, {d_offsets, d_labels}, no_own_checks))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
     if (int rc = score_launch(m, d_bytes, n_bytes, d_offsets, n_docs, d_labels, d_scores, m->d_err, st)) return rc;
-    if (int rc = check_row_error(m, m->d_err, st)) return rc;
-    return ok();
+    return device_call_end(m, st);
 }
 
 namespace {
@@ -2265,10 +2276,15 @@ int check_topk(const ldgpu_model* m, int32_t k) {
         return fail(LDGPU_EINVAL, "k = %d outside [1, min(n_langs = %d, %d)]", k, m->L, LDGPU_MAX_TOPK);
     return LDGPU_OK;
 }
-// the k best of each of nd score rows ([nd][L]) to top_labels [nd][k] and
-// top_scores (nullable) [nd][k]
-hipError_t topk_select(const ldgpu_model* m, const double* scores, int64_t nd, int32_t k, int32_t* top_labels,
-                       double* top_scores, hipStream_t st) {
+
+// One chunk of nd documents: scored through score_launch -- every model kind's
+// own scores path -- into the caller's scratch (`scores` [nd][L], and `raw`
+// [nd], the labels score_launch writes with them), then the k best of each row
+// to top_labels [nd][k] and top_scores (nullable) [nd][k].
+int topk_chunk(ldgpu_model* m, const uint8_t* d_bytes, int64_t n_bytes, const int64_t* d_offsets, int64_t nd,
+               int32_t k, double* scores, int32_t* raw, int32_t* top_labels, double* top_scores, int32_t* d_err,
+               hipStream_t st) {
+    if (int rc = score_launch(m, d_bytes, n_bytes, d_offsets, nd, raw, scores, d_err, st)) return rc;
     TopkParams t{};
     t.scores = scores;
     t.stride = m->L;
@@ -2277,39 +2293,42 @@ hipError_t topk_select(const ldgpu_model* m, const double* scores, int64_t nd, i
     t.k = k;
     t.top_labels = top_labels;
     t.top_scores = top_scores;
-    return launch_topk(t, m->ctx->cus, st);
+    HIP_TRY(launch_topk(t, m->ctx->cus, st));
+    return LDGPU_OK;
 }
-}  // namespace
 
-// Chunks of documents (sub-ranges of d_offsets, whose entries are absolute into
-// d_bytes: nothing is read back) scored into stream-ordered scratch through
-// score_launch -- every model kind's own scores path -- then selected.
-extern "C" int ldgpu_score_topk_device(ldgpu_model* m, const uint8_t* d_bytes, int64_t n_bytes,
-                                       const int64_t* d_offsets, int64_t n_docs, int32_t k, int32_t* d_top_labels,
-                                       double* d_top_scores, void* stream) {
-    const bool null_ptr = n_docs > 0 && (!d_offsets || !d_top_labels || (n_bytes > 0 && !d_bytes));
-    if (int rc = device_call_begin(m, n_docs, d_bytes, null_ptr, [&] { return check_topk(m, k); })) return rc;
-    hipStream_t st = (hipStream_t)stream;
+// The device forms' documents, chunk after chunk (sub-ranges of d_offsets,
+// whose entries are absolute into d_bytes: nothing is read back), each on
+// stream-ordered scratch.
+int topk_device_chunks(ldgpu_model* m, const uint8_t* d_bytes, int64_t n_bytes, const int64_t* d_offsets,
+                       int64_t n_docs, int32_t k, int32_t* d_top_labels, double* d_top_scores, hipStream_t st) {
     const int64_t chunk = topk_chunk_docs(m->L);
     for (int64_t d0 = 0; d0 < n_docs; d0 += chunk) {
         const int64_t nd = std::min(chunk, n_docs - d0);
         const size_t score_bytes = sizeof(double) * (size_t)nd * m->L;
         char* scratch = nullptr;
         HIP_TRY(hipMallocAsync((void**)&scratch, score_bytes + sizeof(int32_t) * (size_t)nd, st));
-        double* sc = (double*)scratch;
-        int rc = score_launch(m, d_bytes, n_bytes, d_offsets + d0, nd, (int32_t*)(scratch + score_bytes), sc, m->d_err,
-                              st);
-        const hipError_t e = rc ? hipSuccess
-                                : topk_select(m, sc, nd, k, d_top_labels + d0 * k,
-                                              d_top_scores ? d_top_scores + d0 * k : nullptr, st);
+        const int rc = topk_chunk(m, d_bytes, n_bytes, d_offsets + d0, nd, k, (double*)scratch,
+                                  (int32_t*)(scratch + score_bytes), d_top_labels + d0 * k,
+                                  d_top_scores ? d_top_scores + d0 * k : nullptr, m->d_err, st);
         (void)hipFreeAsync(scratch, st);
         if (rc) return rc;
-        HIP_TRY(e);
     }
-    if (n_docs > 0) {
-        if (int rc = check_row_error(m, m->d_err, st)) return rc;
-    }
-    return ok();
+    return LDGPU_OK;
+}
+}  // namespace
+
+extern "C" int ldgpu_score_topk_device(ldgpu_model* m, const uint8_t* d_bytes, int64_t n_bytes,
+                                       const int64_t* d_offsets, int64_t n_docs, int32_t k, int32_t* d_top_labels,
+                                       double* d_top_scores, void* stream) {
+    if (int rc = device_call_begin(m, n_docs, n_docs, d_bytes, n_bytes, {d_offsets, d_top_labels},
+                                   [&] { return check_topk(m, k); }))
+        return rc;
+    if (n_docs == 0) return ok();
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = topk_device_chunks(m, d_bytes, n_bytes, d_offsets, n_docs, k, d_top_labels, d_top_scores, st))
+        return rc;
+    return device_call_end(m, st);
 }
 
 // ------------------------------------------------- SCORE: host-buffer calls
@@ -2481,16 +2500,16 @@ int check_host_call(const ldgpu_model* m, const uint8_t* bytes, const int64_t* o
     return LDGPU_OK;
 }
 
-// run(pipeline) on a pipeline of the model's context: thread-safe and
+// A call run on a pipeline of the model's context: thread-safe and
 // concurrent, each call scores on its own (two streams, pinned staging, its
 // own error word), taken from the context's pool
-template <class Run>
-int with_pipe(ldgpu_model* m, Run run) {
+template <class Cut, class Launch>
+int host_call(ldgpu_model* m, const ScoreCall& call, Cut cut, Launch launch) {
     ldgpu_ctx* c = m->ctx;
     HIP_TRY(hipSetDevice(c->device));
     ScorePipe* pp = pipe_acquire(c);
     if (!pp) return LDGPU_EDEVICE;
-    const int rc = run(pp);
+    const int rc = run_score_pipe(m, pp, call, cut, launch);
     pipe_release(c, pp);
     return rc ? rc : ok();
 }
@@ -2509,71 +2528,117 @@ auto doc_chunks(const int64_t* offsets, int64_t n_docs, int64_t max_docs) {
         return PipeChunk{d0, d1, offsets[d0], offsets[d1], d0, d1 - d0};
     };
 }
+
+// The two output tables.  Per item a label, and where asked for a row of L
+// scores and a start: the labels, span and segment forms (an array the form
+// does not have is nullptr) ...
+ScoreCall label_call(const ldgpu_model* m, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs,
+                     const int64_t* span_offsets, int64_t n_items, int32_t* out_labels, double* out_scores,
+                     int64_t* out_starts) {
+    return {bytes, offsets, n_docs, span_offsets, n_items,
+            {{&ScoreStage::labels, &ScoreStage::h_labels, out_labels, sizeof(int32_t)},
+             {&ScoreStage::scores, &ScoreStage::h_scores, out_scores, sizeof(double) * m->L},
+             {&ScoreStage::starts, &ScoreStage::h_starts, out_starts, sizeof(int64_t)}}};
+}
+// ... and per document k labels and k scores: the top-k forms
+ScoreCall topk_call(const uint8_t* bytes, const int64_t* offsets, int64_t n_docs, int32_t k, int32_t* out_top_labels,
+                    double* out_top_scores) {
+    return {bytes, offsets, n_docs, nullptr, n_docs,
+            {{&ScoreStage::top_labels, &ScoreStage::h_labels, out_top_labels, sizeof(int32_t) * k},
+             {&ScoreStage::top_scores, &ScoreStage::h_scores, out_top_scores, sizeof(double) * k}}};
+}
+
+// A host chunk of the top-k forms: scored from (src, src_off) -- the stage's
+// bytes and offsets, or in the UTF-8 form its decoded ones -- into the stage's
+// score buffer (at most kTopkScratchBytes of it), its rows selected on the
+// device, and only the chunk's [nd][k] labels and scores copied back; the
+// stage's [nd] labels serve score_launch alone.  (Both are grown first, before
+// a launch queues anything on the stage: a DevBuf grows with a hipFree.)
+int topk_stage_scratch(const ldgpu_model* m, ScoreStage& st, const PipeChunk& ch) {
+    HIP_TRY(st.labels.ensure(sizeof(int32_t) * (ch.i1 - ch.i0)));
+    HIP_TRY(st.scores.ensure(sizeof(double) * (ch.i1 - ch.i0) * m->L));
+    return LDGPU_OK;
+}
+int topk_stage_chunk(ldgpu_model* m, ScoreStage& st, const PipeChunk& ch, const uint8_t* src, const int64_t* src_off,
+                     int32_t k, bool want_scores, int32_t* d_err) {
+    const int64_t nd = ch.i1 - ch.i0;
+    return topk_chunk(m, src, ch.hi - ch.lo, src_off, nd, k, (double*)st.scores.p, (int32_t*)st.labels.p,
+                      (int32_t*)st.top_labels.p, want_scores ? (double*)st.top_scores.p : nullptr, d_err, st.stream);
+}
 }  // namespace
 
 extern "C" int ldgpu_score(ldgpu_model* m, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs,
                            int32_t* out_labels, double* out_scores) {
     if (int rc = check_host_call(m, bytes, offsets, n_docs, out_labels, "out_labels", true, no_own_checks)) return rc;
     if (n_docs == 0) return ok();
-    const ScoreCall call{bytes, offsets, n_docs, nullptr, n_docs,
-                         {{&ScoreStage::labels, &ScoreStage::h_labels, out_labels, sizeof(int32_t)},
-                          {&ScoreStage::scores, &ScoreStage::h_scores, out_scores, sizeof(double) * m->L}}};
+    const ScoreCall call = label_call(m, bytes, offsets, n_docs, nullptr, n_docs, out_labels, out_scores, nullptr);
     auto launch = [&](ScoreStage& st, const PipeChunk& ch, int32_t* d_err) -> int {
         return score_launch(m, (const uint8_t*)st.bytes.p, ch.hi - ch.lo, (const int64_t*)st.offsets.p, ch.i1 - ch.i0,
                             (int32_t*)st.labels.p, out_scores ? (double*)st.scores.p : nullptr, d_err, st.stream);
     };
-    return with_pipe(m, [&](ScorePipe* pp) {
-        return run_score_pipe(m, pp, call, doc_chunks(offsets, n_docs, score_chunk_docs()), launch);
-    });
+    return host_call(m, call, doc_chunks(offsets, n_docs, score_chunk_docs()), launch);
 }
 
-// Every chunk is scored into the stage's score buffer (at most
-// kTopkScratchBytes of it), its rows selected on the device, and only the
-// chunk's [nd][k] labels and scores copied back; the stage's [nd] labels serve
-// score_launch alone.
 extern "C" int ldgpu_score_topk(ldgpu_model* m, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs,
                                 int32_t k, int32_t* out_top_labels, double* out_top_scores) {
     if (int rc = check_host_call(m, bytes, offsets, n_docs, out_top_labels, "out_top_labels", true,
                                  [&] { return check_topk(m, k); }))
         return rc;
     if (n_docs == 0) return ok();
-    const ScoreCall call{bytes, offsets, n_docs, nullptr, n_docs,
-                         {{&ScoreStage::top_labels, &ScoreStage::h_labels, out_top_labels, sizeof(int32_t) * k},
-                          {&ScoreStage::top_scores, &ScoreStage::h_scores, out_top_scores, sizeof(double) * k}}};
     auto launch = [&](ScoreStage& st, const PipeChunk& ch, int32_t* d_err) -> int {
-        const int64_t nd = ch.i1 - ch.i0;
-        HIP_TRY(st.labels.ensure(sizeof(int32_t) * nd));
-        HIP_TRY(st.scores.ensure(sizeof(double) * nd * m->L));
-        if (int r = score_launch(m, (const uint8_t*)st.bytes.p, ch.hi - ch.lo, (const int64_t*)st.offsets.p, nd,
-                                 (int32_t*)st.labels.p, (double*)st.scores.p, d_err, st.stream))
-            return r;
-        HIP_TRY(topk_select(m, (const double*)st.scores.p, nd, k, (int32_t*)st.top_labels.p,
-                            out_top_scores ? (double*)st.top_scores.p : nullptr, st.stream));
-        return LDGPU_OK;
+        if (int r = topk_stage_scratch(m, st, ch)) return r;
+        return topk_stage_chunk(m, st, ch, (const uint8_t*)st.bytes.p, (const int64_t*)st.offsets.p, k,
+                                out_top_scores != nullptr, d_err);
     };
     const int64_t max_docs = std::min(score_chunk_docs(), topk_chunk_docs(m->L));
-    return with_pipe(m, [&](ScorePipe* pp) {
-        return run_score_pipe(m, pp, call, doc_chunks(offsets, n_docs, max_docs), launch);
-    });
+    return host_call(m, topk_call(bytes, offsets, n_docs, k, out_top_labels, out_top_scores),
+                     doc_chunks(offsets, n_docs, max_docs), launch);
 }
 
 // ------------------------------------------------------------- SCORE: UTF-8
 // UTF-8 documents scored without a host transcode (include/ldgpu.h): decoded
 // to the SCORE encoding on the device (ldgpu_utf8.hip), the decoded corpus fed
-// to score_launch -- every model kind's own path -- and the label of an
-// ill-formed document (decoded to nothing, so its score row is the empty
-// document's) set to -1 afterwards.
+// to the byte form's own body -- score_launch, every model kind's own path, in
+// the labels form -- and the label of an ill-formed document (decoded to
+// nothing, so its score row is the empty document's) set to -1 afterwards.
 namespace {
+// Where documents are decoded to: the SCORE bytes -- at most as many as the
+// UTF-8 bytes, and slack --, the decoded offsets [n_docs + 1] and the
+// ill-formed flags [n_docs].  The host forms give a stage's grow-only buffers,
+// the device forms one block of stream-ordered scratch (freed at `dec`).
+struct UtfBufs {
+    uint8_t* dec = nullptr;
+    int64_t* dec_off = nullptr;
+    uint8_t* host = nullptr;
+};
+int utf_stage_bufs(ScoreStage& st, int64_t n_docs, int64_t n_bytes, UtfBufs* u) {
+    HIP_TRY(st.dec.ensure((size_t)n_bytes + 16));
+    HIP_TRY(st.dec_offsets.ensure(sizeof(int64_t) * (size_t)(n_docs + 1)));
+    HIP_TRY(st.dec_host.ensure((size_t)n_docs));
+    *u = {(uint8_t*)st.dec.p, (int64_t*)st.dec_offsets.p, (uint8_t*)st.dec_host.p};
+    return LDGPU_OK;
+}
+int utf_scratch_bufs(int64_t n_docs, int64_t n_bytes, UtfBufs* u, hipStream_t st) {
+    const size_t a_dec = up256((size_t)n_bytes + 16), a_off = up256(sizeof(int64_t) * (size_t)(n_docs + 1));
+    char* p = nullptr;
+    HIP_TRY(hipMallocAsync((void**)&p, a_dec + a_off + (size_t)n_docs + 16, st));
+    *u = {(uint8_t*)p, (int64_t*)(p + a_dec), (uint8_t*)(p + a_dec + a_off)};
+    return LDGPU_OK;
+}
+int utf_decode(ldgpu_model* m, const uint8_t* d_utf8, const int64_t* d_offsets, int64_t n_docs, const UtfBufs& u,
+               hipStream_t st) {
+    return utf8_decode_launch(m->ctx->cus, d_utf8, d_offsets, n_docs, LDGPU_PRE_LOW_BYTES, u.dec, u.dec_off, u.host,
+                              st);
+}
+
 // the decoded bytes number at most the UTF-8 bytes (n_bytes, which score_launch
-// then takes as the readable size of d_dec: the scratch holds that and slack)
+// then takes as the readable size of u.dec: the buffer holds that and slack)
 int score_utf8_launch(ldgpu_model* m, const uint8_t* d_utf8, int64_t n_bytes, const int64_t* d_offsets,
-                      int64_t n_docs, uint8_t* d_dec, int64_t* d_dec_off, uint8_t* d_host, int32_t* d_labels,
-                      double* d_scores, int32_t* d_err, hipStream_t st) {
-    if (int rc = utf8_decode_launch(m->ctx->cus, d_utf8, d_offsets, n_docs, LDGPU_PRE_LOW_BYTES, d_dec, d_dec_off,
-                                    d_host, st))
-        return rc;
-    if (int rc = score_launch(m, d_dec, n_bytes, d_dec_off, n_docs, d_labels, d_scores, d_err, st)) return rc;
-    HIP_TRY(launch_utf8_labels(d_host, n_docs, d_labels, m->ctx->cus, st));
+                      int64_t n_docs, const UtfBufs& u, int32_t* d_labels, double* d_scores, int32_t* d_err,
+                      hipStream_t st) {
+    if (int rc = utf_decode(m, d_utf8, d_offsets, n_docs, u, st)) return rc;
+    if (int rc = score_launch(m, u.dec, n_bytes, u.dec_off, n_docs, d_labels, d_scores, d_err, st)) return rc;
+    HIP_TRY(launch_utf8_labels(u.host, n_docs, d_labels, m->ctx->cus, st));
     return LDGPU_OK;
 }
 
@@ -2590,21 +2655,15 @@ extern "C" int ldgpu_score_utf8(ldgpu_model* m, const uint8_t* utf8, const int64
                                 int32_t* out_labels, double* out_scores) {
     if (int rc = check_host_call(m, utf8, offsets, n_docs, out_labels, "out_labels", true, no_own_checks)) return rc;
     if (n_docs == 0) return ok();
-    const ScoreCall call{utf8, offsets, n_docs, nullptr, n_docs,
-                         {{&ScoreStage::labels, &ScoreStage::h_labels, out_labels, sizeof(int32_t)},
-                          {&ScoreStage::scores, &ScoreStage::h_scores, out_scores, sizeof(double) * m->L}}};
+    const ScoreCall call = label_call(m, utf8, offsets, n_docs, nullptr, n_docs, out_labels, out_scores, nullptr);
     auto launch = [&](ScoreStage& st, const PipeChunk& ch, int32_t* d_err) -> int {
         const int64_t nd = ch.i1 - ch.i0, nb = ch.hi - ch.lo;
-        HIP_TRY(st.dec.ensure((size_t)nb + 16));
-        HIP_TRY(st.dec_offsets.ensure(sizeof(int64_t) * (size_t)(nd + 1)));
-        HIP_TRY(st.dec_host.ensure((size_t)nd));
-        return score_utf8_launch(m, (const uint8_t*)st.bytes.p, nb, (const int64_t*)st.offsets.p, nd,
-                                 (uint8_t*)st.dec.p, (int64_t*)st.dec_offsets.p, (uint8_t*)st.dec_host.p,
+        UtfBufs u;
+        if (int r = utf_stage_bufs(st, nd, nb, &u)) return r;
+        return score_utf8_launch(m, (const uint8_t*)st.bytes.p, nb, (const int64_t*)st.offsets.p, nd, u,
                                  (int32_t*)st.labels.p, out_scores ? (double*)st.scores.p : nullptr, d_err, st.stream);
     };
-    return with_pipe(m, [&](ScorePipe* pp) {
-        return run_score_pipe(m, pp, call, doc_chunks(offsets, n_docs, score_chunk_docs()), launch);
-    });
+    return host_call(m, call, doc_chunks(offsets, n_docs, score_chunk_docs()), launch);
 }
 
 // Chunks of documents (sub-ranges of d_offsets, absolute into d_utf8: nothing
@@ -2614,28 +2673,23 @@ extern "C" int ldgpu_score_utf8(ldgpu_model* m, const uint8_t* utf8, const int64
 extern "C" int ldgpu_score_utf8_device(ldgpu_model* m, const uint8_t* d_utf8, int64_t n_bytes,
                                        const int64_t* d_offsets, int64_t n_docs, int32_t* d_labels, double* d_scores,
                                        void* stream) {
-    const bool null_ptr = n_docs > 0 && (!d_offsets || !d_labels || (n_bytes > 0 && !d_utf8));
-    if (int rc = device_call_begin(m, n_docs, d_utf8, null_ptr, [&] {
+    if (int rc = device_call_begin(m, n_docs, n_docs, d_utf8, n_bytes, {d_offsets, d_labels}, [&] {
             return n_bytes < 0 ? fail(LDGPU_EINVAL, "n_bytes < 0") : (int)LDGPU_OK;
         }))
         return rc;
+    if (n_docs == 0) return ok();
     hipStream_t st = (hipStream_t)stream;
     const int64_t chunk = utf8_chunk_docs();
     for (int64_t d0 = 0; d0 < n_docs; d0 += chunk) {
         const int64_t nd = std::min(chunk, n_docs - d0);
-        const size_t a_dec = ((size_t)n_bytes + 16 + 15) & ~(size_t)15, a_off = sizeof(int64_t) * (size_t)(nd + 1);
-        char* scratch = nullptr;
-        HIP_TRY(hipMallocAsync((void**)&scratch, a_dec + a_off + (size_t)nd, st));
-        const int rc = score_utf8_launch(m, d_utf8, n_bytes, d_offsets + d0, nd, (uint8_t*)scratch,
-                                         (int64_t*)(scratch + a_dec), (uint8_t*)(scratch + a_dec + a_off),
-                                         d_labels + d0, d_scores ? d_scores + (size_t)d0 * m->L : nullptr, m->d_err, st);
-        (void)hipFreeAsync(scratch, st);
+        UtfBufs u;
+        if (int rc = utf_scratch_bufs(nd, n_bytes, &u, st)) return rc;
+        const int rc = score_utf8_launch(m, d_utf8, n_bytes, d_offsets + d0, nd, u, d_labels + d0,
+                                         d_scores ? d_scores + (size_t)d0 * m->L : nullptr, m->d_err, st);
+        (void)hipFreeAsync(u.dec, st);
         if (rc) return rc;
     }
-    if (n_docs > 0) {
-        if (int rc = check_row_error(m, m->d_err, st)) return rc;
-    }
-    return ok();
+    return device_call_end(m, st);
 }
 
 // ------------------------------------------------------------- SCORE: spans
@@ -2674,7 +2728,28 @@ void host_span_offsets(const int64_t* offsets, int64_t n_docs, int32_t width, in
     }
     span_offsets[n_docs] = g;
 }
-size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// Where a chunk's score rows go to a buffer of the call's own -- the host
+// forms' stage, the segment forms' scratch -- that buffer bounds the chunk
+// too, as in the top-k form.
+int64_t span_budget(const ldgpu_model* m, int32_t width, bool own_scores) {
+    const int64_t n = span_chunk_spans(width);
+    return own_scores ? std::min(n, topk_chunk_docs(m->L)) : n;
+}
+
+// the corpus as the span kernels see it (g0 / nc: the chunk's, set per chunk)
+SpanParams span_corpus(const uint8_t* bytes, int64_t n_bytes, const int64_t* offsets, int64_t n_docs,
+                       const int64_t* span_offsets, int32_t width, int32_t stride) {
+    SpanParams sp{};
+    sp.bytes = bytes;
+    sp.n_bytes = n_bytes;
+    sp.offsets = offsets;
+    sp.n_docs = n_docs;
+    sp.span_offsets = span_offsets;
+    sp.width = width;
+    sp.stride = stride;
+    return sp;
+}
 
 // One chunk -- the spans [sp.g0, sp.g0 + sp.nc) of the corpus sp describes --
 // gathered into stream-ordered scratch and scored from there: labels to
@@ -2702,6 +2777,59 @@ int span_chunk(ldgpu_model* m, SpanParams sp, int32_t* d_labels, double* d_score
     HIP_TRY(e);
     return rc;
 }
+
+// the spans [0, n_spans) of the corpus sp describes, chunk after chunk; the
+// labels and scores of a chunk go straight to d_labels / d_scores
+int span_chunks(ldgpu_model* m, SpanParams sp, int64_t n_spans, int64_t chunk, int32_t* d_labels, double* d_scores,
+                int32_t* d_err, hipStream_t st) {
+    for (int64_t g0 = 0; g0 < n_spans; g0 += chunk) {
+        sp.g0 = g0;
+        sp.nc = std::min(chunk, n_spans - g0);
+        if (int rc = span_chunk(m, sp, d_labels + g0, d_scores ? d_scores + g0 * m->L : nullptr, d_err, st)) return rc;
+    }
+    return LDGPU_OK;
+}
+
+// A host cut at document boundaries: whole documents from the one whose first
+// span is g0 (a chunk starts at a document's first span: g0 is one of soff),
+// as many as fit `budget` spans and kScoreChunkBytes of source bytes, one at
+// least.
+auto span_doc_chunks(const int64_t* offsets, const int64_t* soff, int64_t n_docs, int64_t budget) {
+    return [=](int64_t g0) {
+        const int64_t d0 = (int64_t)(std::upper_bound(soff, soff + n_docs, g0) - soff) - 1;
+        int64_t d1 = d0 + 1;
+        while (d1 < n_docs && soff[d1 + 1] - soff[d0] <= budget && offsets[d1 + 1] - offsets[d0] <= kScoreChunkBytes)
+            ++d1;
+        return PipeChunk{soff[d0], soff[d1], offsets[d0], offsets[d1], d0, d1 - d0};
+    };
+}
+
+// A host chunk's corpus: its documents in (src, src_off) -- the stage's bytes
+// and offsets, or in the UTF-8 forms its decoded ones -- and its span offsets,
+// which the stage holds behind the document offsets.
+const int64_t* stage_span_offsets(const ScoreStage& st, const PipeChunk& ch) {
+    return (const int64_t*)st.offsets.p + ch.n_docs + 1;
+}
+SpanParams stage_corpus(const ScoreStage& st, const PipeChunk& ch, const uint8_t* src, const int64_t* src_off,
+                        int32_t width, int32_t stride) {
+    return span_corpus(src, ch.hi - ch.lo, src_off, ch.n_docs, stage_span_offsets(st, ch), width, stride);
+}
+// ... and its spans scored into the stage's labels and scores
+int stage_spans(ldgpu_model* m, ScoreStage& st, const PipeChunk& ch, const uint8_t* src, const int64_t* src_off,
+                int32_t width, int32_t stride, int64_t budget, bool want_scores, int32_t* d_err) {
+    return span_chunks(m, stage_corpus(st, ch, src, src_off, width, stride), ch.i1 - ch.i0, budget,
+                       (int32_t*)st.labels.p, want_scores ? (double*)st.scores.p : nullptr, d_err, st.stream);
+}
+
+// the checks the two device span-offset calls share, in their order
+int check_span_offsets_device(const ldgpu_ctx* ctx, int64_t n_docs, int32_t width, int32_t stride,
+                              const int64_t* d_offsets, const int64_t* d_span_offsets) {
+    if (!ctx) return fail(LDGPU_EINVAL, "context is NULL");
+    if (n_docs < 0) return fail(LDGPU_EINVAL, "n_docs < 0");
+    if (int rc = check_span_args(width, stride)) return rc;
+    if (!d_span_offsets || (n_docs > 0 && !d_offsets)) return fail(LDGPU_EINVAL, "device pointer is NULL");
+    return LDGPU_OK;
+}
 }  // namespace
 
 extern "C" int ldgpu_span_offsets(const int64_t* offsets, int64_t n_docs, int32_t width, int32_t stride,
@@ -2715,10 +2843,7 @@ extern "C" int ldgpu_span_offsets(const int64_t* offsets, int64_t n_docs, int32_
 
 extern "C" int ldgpu_span_offsets_device(ldgpu_ctx* ctx, const int64_t* d_offsets, int64_t n_docs, int32_t width,
                                          int32_t stride, int64_t* d_span_offsets, void* stream) {
-    if (!ctx) return fail(LDGPU_EINVAL, "context is NULL");
-    if (n_docs < 0) return fail(LDGPU_EINVAL, "n_docs < 0");
-    if (int rc = check_span_args(width, stride)) return rc;
-    if (!d_span_offsets || (n_docs > 0 && !d_offsets)) return fail(LDGPU_EINVAL, "device pointer is NULL");
+    if (int rc = check_span_offsets_device(ctx, n_docs, width, stride, d_offsets, d_span_offsets)) return rc;
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(ctx->device));
     size_t scan_bytes = 0;
@@ -2739,32 +2864,16 @@ extern "C" int ldgpu_score_spans_device(ldgpu_model* m, const uint8_t* d_bytes, 
                                         const int64_t* d_offsets, int64_t n_docs, int32_t width, int32_t stride,
                                         const int64_t* d_span_offsets, int64_t n_spans, int32_t* d_labels,
                                         double* d_scores, void* stream) {
-    const bool null_ptr = n_spans > 0 && (!d_offsets || !d_span_offsets || !d_labels || (n_bytes > 0 && !d_bytes));
-    if (int rc = device_call_begin(m, n_docs, d_bytes, null_ptr, [&] {
+    if (int rc = device_call_begin(m, n_docs, n_spans, d_bytes, n_bytes, {d_offsets, d_span_offsets, d_labels}, [&] {
             if (n_spans < 0) return fail(LDGPU_EINVAL, "n_spans < 0");
             return check_span_args(width, stride);
         }))
         return rc;
+    if (n_spans == 0) return ok();
     hipStream_t st = (hipStream_t)stream;
-    const int64_t chunk = span_chunk_spans(width);
-    for (int64_t g0 = 0; g0 < n_spans; g0 += chunk) {
-        SpanParams sp{};
-        sp.bytes = d_bytes;
-        sp.n_bytes = n_bytes;
-        sp.offsets = d_offsets;
-        sp.n_docs = n_docs;
-        sp.span_offsets = d_span_offsets;
-        sp.width = width;
-        sp.stride = stride;
-        sp.g0 = g0;
-        sp.nc = std::min(chunk, n_spans - g0);
-        if (int rc = span_chunk(m, sp, d_labels + g0, d_scores ? d_scores + g0 * m->L : nullptr, m->d_err, st))
-            return rc;
-    }
-    if (n_spans > 0) {
-        if (int rc = check_row_error(m, m->d_err, st)) return rc;
-    }
-    return ok();
+    const SpanParams sp = span_corpus(d_bytes, n_bytes, d_offsets, n_docs, d_span_offsets, width, stride);
+    if (int rc = span_chunks(m, sp, n_spans, span_chunk_spans(width), d_labels, d_scores, m->d_err, st)) return rc;
+    return device_call_end(m, st);
 }
 
 // The span form of the host pipeline (run_score_pipe): chunks are fixed runs of
@@ -2784,12 +2893,8 @@ extern "C" int ldgpu_score_spans(ldgpu_model* m, const uint8_t* bytes, const int
     std::vector<int64_t> soff((size_t)n_docs + 1);
     host_span_offsets(offsets, n_docs, width, stride, soff.data());
     const int64_t n_spans = soff[n_docs];
-    const ScoreCall call{bytes, offsets, n_docs, soff.data(), n_spans,
-                         {{&ScoreStage::labels, &ScoreStage::h_labels, out_labels, sizeof(int32_t)},
-                          {&ScoreStage::scores, &ScoreStage::h_scores, out_scores, sizeof(double) * m->L}}};
-    // (with scores the stage's score buffer bounds a chunk too, as in the top-k form)
-    int64_t chunk = span_chunk_spans(width);
-    if (out_scores) chunk = std::min(chunk, topk_chunk_docs(m->L));
+    const ScoreCall call = label_call(m, bytes, offsets, n_docs, soff.data(), n_spans, out_labels, out_scores, nullptr);
+    const int64_t chunk = span_budget(m, width, out_scores != nullptr);
     // the last document d with soff[d] <= g
     auto doc_of = [&](int64_t g) -> int64_t {
         return (int64_t)(std::upper_bound(soff.begin(), soff.begin() + n_docs, g) - soff.begin()) - 1;
@@ -2802,19 +2907,10 @@ extern "C" int ldgpu_score_spans(ldgpu_model* m, const uint8_t* bytes, const int
         return PipeChunk{g0, g1, lo, hi, dA, dB - dA + 1};
     };
     auto launch = [&](ScoreStage& st, const PipeChunk& ch, int32_t* d_err) -> int {
-        SpanParams sp{};
-        sp.bytes = (const uint8_t*)st.bytes.p;
-        sp.n_bytes = ch.hi - ch.lo;
-        sp.offsets = (const int64_t*)st.offsets.p;
-        sp.n_docs = ch.n_docs;
-        sp.span_offsets = sp.offsets + ch.n_docs + 1;
-        sp.width = width;
-        sp.stride = stride;
-        sp.g0 = 0;
-        sp.nc = ch.i1 - ch.i0;
-        return span_chunk(m, sp, (int32_t*)st.labels.p, out_scores ? (double*)st.scores.p : nullptr, d_err, st.stream);
+        return stage_spans(m, st, ch, (const uint8_t*)st.bytes.p, (const int64_t*)st.offsets.p, width, stride, chunk,
+                           out_scores != nullptr, d_err);
     };
-    return with_pipe(m, [&](ScorePipe* pp) { return run_score_pipe(m, pp, call, cut, launch); });
+    return host_call(m, call, cut, launch);
 }
 
 // ---------------------------------------------------------- SCORE: segments
@@ -2859,7 +2955,7 @@ int segments_launch(ldgpu_model* m, SpanParams sp, double penalty, int64_t n_spa
     g.arg = (int32_t*)(scratch + n_sw);
     double* carry = (double*)(scratch + n_sw + n_arg);
     g.labels = d_labels;
-    const int64_t chunk = std::min(span_chunk_spans(sp.width), topk_chunk_docs(m->L));
+    const int64_t chunk = span_budget(m, sp.width, true);
     int rc = LDGPU_OK;
     hipError_t e = hipSuccess;
     int64_t k = 0;
@@ -2892,42 +2988,39 @@ int segments_launch(ldgpu_model* m, SpanParams sp, double penalty, int64_t n_spa
     HIP_TRY(e);
     return LDGPU_OK;
 }
+
+// a host chunk's smoothed labels from (src, src_off), as stage_spans
+int stage_segments(ldgpu_model* m, ScoreStage& st, const PipeChunk& ch, const uint8_t* src, const int64_t* src_off,
+                   int32_t width, int32_t stride, double penalty, int32_t* d_err) {
+    return segments_launch(m, stage_corpus(st, ch, src, src_off, width, stride), penalty, ch.i1 - ch.i0,
+                           (int32_t*)st.labels.p, d_err, st.stream);
+}
 }  // namespace
 
 extern "C" int ldgpu_score_segments_device(ldgpu_model* m, const uint8_t* d_bytes, int64_t n_bytes,
                                            const int64_t* d_offsets, int64_t n_docs, int32_t width, int32_t stride,
                                            double penalty, const int64_t* d_span_offsets, int64_t n_spans,
                                            int32_t* d_labels, void* stream) {
-    const bool null_ptr = n_spans > 0 && (!d_offsets || !d_span_offsets || !d_labels || (n_bytes > 0 && !d_bytes));
-    if (int rc = device_call_begin(m, n_docs, d_bytes, null_ptr, [&] {
+    if (int rc = device_call_begin(m, n_docs, n_spans, d_bytes, n_bytes, {d_offsets, d_span_offsets, d_labels}, [&] {
             if (n_spans < 0) return fail(LDGPU_EINVAL, "n_spans < 0");
             if (int r = check_span_args(width, stride)) return r;
             return check_penalty(penalty);
         }))
         return rc;
+    if (n_spans == 0) return ok();
     hipStream_t st = (hipStream_t)stream;
-    SpanParams sp{};
-    sp.bytes = d_bytes;
-    sp.n_bytes = n_bytes;
-    sp.offsets = d_offsets;
-    sp.n_docs = n_docs;
-    sp.span_offsets = d_span_offsets;
-    sp.width = width;
-    sp.stride = stride;
+    const SpanParams sp = span_corpus(d_bytes, n_bytes, d_offsets, n_docs, d_span_offsets, width, stride);
     if (int rc = segments_launch(m, sp, penalty, n_spans, d_labels, m->d_err, st)) return rc;
-    if (n_spans > 0) {
-        if (int rc = check_row_error(m, m->d_err, st)) return rc;
-    }
-    return ok();
+    return device_call_end(m, st);
 }
 
 // The segment form of the host pipeline (run_score_pipe).  A document's labels
 // are known only after its last span, and the pipeline hands a chunk's outputs
 // back when the chunk retires: so, unlike the span form's, a chunk ends at a
 // document boundary -- as many whole documents as fit the span budget
-// (span_chunk_spans) and kScoreChunkBytes of source bytes, one at least.  A
-// single document beyond the budget is a chunk of its own, which
-// segments_launch cuts into span chunks with carry.
+// (span_chunk_spans) and kScoreChunkBytes of source bytes, one at least
+// (span_doc_chunks).  A single document beyond the budget is a chunk of its
+// own, which segments_launch cuts into span chunks with carry.
 extern "C" int ldgpu_score_segments(ldgpu_model* m, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs,
                                     int32_t width, int32_t stride, double penalty, int32_t* out_labels) {
     // (no document-length limit, as in the span form)
@@ -2939,37 +3032,19 @@ extern "C" int ldgpu_score_segments(ldgpu_model* m, const uint8_t* bytes, const 
     if (n_docs == 0) return ok();
     std::vector<int64_t> soff((size_t)n_docs + 1);
     host_span_offsets(offsets, n_docs, width, stride, soff.data());
-    const int64_t n_spans = soff[n_docs];
-    const ScoreCall call{bytes, offsets, n_docs, soff.data(), n_spans,
-                         {{&ScoreStage::labels, &ScoreStage::h_labels, out_labels, sizeof(int32_t)},
-                          {&ScoreStage::scores, &ScoreStage::h_scores, nullptr, 0}}};
-    const int64_t budget = span_chunk_spans(width);
-    // (a chunk starts at a document's first span: g0 is one of soff)
-    auto cut = [&](int64_t g0) {
-        const int64_t d0 = (int64_t)(std::upper_bound(soff.begin(), soff.begin() + n_docs, g0) - soff.begin()) - 1;
-        int64_t d1 = d0 + 1;
-        while (d1 < n_docs && soff[d1 + 1] - soff[d0] <= budget && offsets[d1 + 1] - offsets[d0] <= kScoreChunkBytes)
-            ++d1;
-        return PipeChunk{soff[d0], soff[d1], offsets[d0], offsets[d1], d0, d1 - d0};
-    };
+    const ScoreCall call = label_call(m, bytes, offsets, n_docs, soff.data(), soff[n_docs], out_labels, nullptr,
+                                      nullptr);
     auto launch = [&](ScoreStage& st, const PipeChunk& ch, int32_t* d_err) -> int {
-        SpanParams sp{};
-        sp.bytes = (const uint8_t*)st.bytes.p;
-        sp.n_bytes = ch.hi - ch.lo;
-        sp.offsets = (const int64_t*)st.offsets.p;
-        sp.n_docs = ch.n_docs;
-        sp.span_offsets = sp.offsets + ch.n_docs + 1;
-        sp.width = width;
-        sp.stride = stride;
-        return segments_launch(m, sp, penalty, ch.i1 - ch.i0, (int32_t*)st.labels.p, d_err, st.stream);
+        return stage_segments(m, st, ch, (const uint8_t*)st.bytes.p, (const int64_t*)st.offsets.p, width, stride,
+                              penalty, d_err);
     };
-    return with_pipe(m, [&](ScorePipe* pp) { return run_score_pipe(m, pp, call, cut, launch); });
+    return host_call(m, call, span_doc_chunks(offsets, soff.data(), n_docs, span_chunk_spans(width)), launch);
 }
 
 // ------------------------------------- SCORE: UTF-8 top-k, spans, segments
 // The three remaining forms on UTF-8 documents (the rule: include/ldgpu.h
 // UTF-8: top-k, spans, segments).  Every form decodes to the SCORE encoding
-// first (ldgpu_utf8.hip) and then runs its twin's own launch on the decoded
+// first (ldgpu_utf8.hip) and then runs its twin's own body on the decoded
 // corpus; the span starts come from a kernel over the UTF-8 itself, the labels
 // of ill-formed documents are set last.
 namespace {
@@ -2979,57 +3054,64 @@ int check_utf_docs(int64_t n_docs) {
     return LDGPU_OK;
 }
 
-// a device-form call's decode scratch on st: n_bytes (+ slack) of low bytes,
-// the decoded offsets and the flags of n_docs documents
-struct UtfScratch {
-    char* p = nullptr;
-    uint8_t* dec = nullptr;
-    int64_t* dec_off = nullptr;
-    uint8_t* host = nullptr;
-};
-int utf_scratch_decode(ldgpu_model* m, const uint8_t* d_utf8, int64_t n_bytes, const int64_t* d_offsets,
-                       int64_t n_docs, UtfScratch* s, hipStream_t st) {
-    const size_t a_dec = ((size_t)n_bytes + 16 + 255) & ~(size_t)255, a_off = up256(sizeof(int64_t) * (size_t)(n_docs + 1));
-    HIP_TRY(hipMallocAsync((void**)&s->p, a_dec + a_off + (size_t)n_docs + 16, st));
-    s->dec = (uint8_t*)s->p;
-    s->dec_off = (int64_t*)(s->p + a_dec);
-    s->host = (uint8_t*)(s->p + a_dec + a_off);
-    const int rc = utf8_decode_launch(m->ctx->cus, d_utf8, d_offsets, n_docs, LDGPU_PRE_LOW_BYTES, s->dec, s->dec_off,
-                                      s->host, st);
-    if (rc) (void)hipFreeAsync(s->p, st);
-    return rc;
+// The top-k forms on the buffers u: the documents decoded, `twin` -- the byte
+// form's body, given the decoded corpus -- then the rows of the ill-formed
+// documents.
+template <class Twin>
+int utf_topk(ldgpu_model* m, const uint8_t* d_utf8, const int64_t* d_offsets, int64_t n_docs, const UtfBufs& u,
+             int32_t k, int32_t* d_top_labels, double* d_top_scores, hipStream_t st, Twin twin) {
+    if (int rc = utf_decode(m, d_utf8, d_offsets, n_docs, u, st)) return rc;
+    if (int rc = twin(u.dec, u.dec_off)) return rc;
+    HIP_TRY(launch_utf8_topk_labels(u.host, n_docs, k, d_top_labels, d_top_scores, m->ctx->cus, st));
+    return LDGPU_OK;
 }
 
-// after the decoded corpus is scored: the span starts (d_starts nullable: no
-// work at all) and the -1 labels of the ill-formed documents
-int utf_span_finish(ldgpu_model* m, const uint8_t* d_utf8, const int64_t* d_offsets, int64_t n_docs,
-                    const uint8_t* d_host, const int64_t* d_span_offsets, int64_t n_spans, int32_t stride,
-                    int32_t* d_labels, int64_t* d_starts, hipStream_t st) {
+// The span and segment forms on the buffers u: the documents decoded, `twin`
+// -- the byte form's body, given the decoded corpus -- then the span starts
+// (d_starts nullable: no work at all) and the -1 labels of the ill-formed
+// documents.
+template <class Twin>
+int utf_spans(ldgpu_model* m, const uint8_t* d_utf8, const int64_t* d_offsets, int64_t n_docs, const UtfBufs& u,
+              const int64_t* d_span_offsets, int64_t n_spans, int32_t stride, int32_t* d_labels, int64_t* d_starts,
+              hipStream_t st, Twin twin) {
+    if (int rc = utf_decode(m, d_utf8, d_offsets, n_docs, u, st)) return rc;
+    if (int rc = twin(u.dec, u.dec_off)) return rc;
     if (d_starts) {
         Utf8StartParams q{};
         q.utf8 = d_utf8;
         q.offsets = d_offsets;
         q.n_docs = n_docs;
-        q.host = d_host;
+        q.host = u.host;
         q.span_offsets = d_span_offsets;
         q.n_spans = n_spans;
         q.stride = stride;
         q.starts = d_starts;
         HIP_TRY(launch_utf8_starts(q, m->ctx->cus, st));
     }
-    HIP_TRY(launch_utf8_span_labels(d_host, d_span_offsets, n_docs, n_spans, d_labels, m->ctx->cus, st));
+    HIP_TRY(launch_utf8_span_labels(u.host, d_span_offsets, n_docs, n_spans, d_labels, m->ctx->cus, st));
     return LDGPU_OK;
 }
-
-// the spans [0, n_spans) of the corpus sp describes, chunk after chunk
-int span_chunks(ldgpu_model* m, SpanParams sp, int64_t n_spans, int64_t chunk, int32_t* d_labels, double* d_scores,
-                int32_t* d_err, hipStream_t st) {
-    for (int64_t g0 = 0; g0 < n_spans; g0 += chunk) {
-        sp.g0 = g0;
-        sp.nc = std::min(chunk, n_spans - g0);
-        if (int rc = span_chunk(m, sp, d_labels + g0, d_scores ? d_scores + g0 * m->L : nullptr, d_err, st)) return rc;
-    }
-    return LDGPU_OK;
+// ... of a device call, the whole call decoded into stream-ordered scratch
+template <class Twin>
+int device_utf_spans(ldgpu_model* m, const uint8_t* d_utf8, int64_t n_bytes, const int64_t* d_offsets, int64_t n_docs,
+                     const int64_t* d_span_offsets, int64_t n_spans, int32_t stride, int32_t* d_labels,
+                     int64_t* d_starts, hipStream_t st, Twin twin) {
+    UtfBufs u;
+    if (int rc = utf_scratch_bufs(n_docs, n_bytes, &u, st)) return rc;
+    const int rc = utf_spans(m, d_utf8, d_offsets, n_docs, u, d_span_offsets, n_spans, stride, d_labels, d_starts, st,
+                             twin);
+    (void)hipFreeAsync(u.dec, st);
+    return rc;
+}
+// ... of a host chunk (st.bytes and st.offsets hold its UTF-8), decoded into
+// the stage's buffers
+template <class Twin>
+int stage_utf_spans(ldgpu_model* m, ScoreStage& st, const PipeChunk& ch, int32_t stride, bool want_starts, Twin twin) {
+    UtfBufs u;
+    if (int r = utf_stage_bufs(st, ch.n_docs, ch.hi - ch.lo, &u)) return r;
+    return utf_spans(m, (const uint8_t*)st.bytes.p, (const int64_t*)st.offsets.p, ch.n_docs, u,
+                     stage_span_offsets(st, ch), ch.i1 - ch.i0, stride, (int32_t*)st.labels.p,
+                     want_starts ? (int64_t*)st.starts.p : nullptr, st.stream, twin);
 }
 
 // the host forms' span_offsets: [n_docs + 1] from 0, every document a span
@@ -3041,37 +3123,12 @@ int check_span_offsets(const int64_t* span_offsets, int64_t n_docs) {
             return fail(LDGPU_EINVAL, "span_offsets decrease or leave document %lld without a span", (long long)d);
     return LDGPU_OK;
 }
-
-// whole documents from the one whose first span is g0: as many as fit `budget`
-// spans and kScoreChunkBytes of source bytes, one at least (ldgpu_score_segments' cut)
-auto span_doc_chunks(const int64_t* offsets, const int64_t* soff, int64_t n_docs, int64_t budget) {
-    return [=](int64_t g0) {
-        const int64_t d0 = (int64_t)(std::upper_bound(soff, soff + n_docs, g0) - soff) - 1;
-        int64_t d1 = d0 + 1;
-        while (d1 < n_docs && soff[d1 + 1] - soff[d0] <= budget && offsets[d1 + 1] - offsets[d0] <= kScoreChunkBytes)
-            ++d1;
-        return PipeChunk{soff[d0], soff[d1], offsets[d0], offsets[d1], d0, d1 - d0};
-    };
-}
-
-// a host chunk's UTF-8 (st.bytes, st.offsets) decoded into the stage's buffers
-int stage_decode(ldgpu_model* m, ScoreStage& st, int64_t nd, int64_t nb) {
-    HIP_TRY(st.dec.ensure((size_t)nb + 16));
-    HIP_TRY(st.dec_offsets.ensure(sizeof(int64_t) * (size_t)(nd + 1)));
-    HIP_TRY(st.dec_host.ensure((size_t)nd));
-    return utf8_decode_launch(m->ctx->cus, (const uint8_t*)st.bytes.p, (const int64_t*)st.offsets.p, nd,
-                              LDGPU_PRE_LOW_BYTES, st.dec.p, (int64_t*)st.dec_offsets.p, (uint8_t*)st.dec_host.p,
-                              st.stream);
-}
 }  // namespace
 
 extern "C" int ldgpu_span_offsets_utf_device(ldgpu_ctx* ctx, const uint8_t* d_utf8, const int64_t* d_offsets,
                                              int64_t n_docs, int32_t width, int32_t stride, int64_t* d_span_offsets,
                                              int64_t* d_units, void* stream) {
-    if (!ctx) return fail(LDGPU_EINVAL, "context is NULL");
-    if (n_docs < 0) return fail(LDGPU_EINVAL, "n_docs < 0");
-    if (int rc = check_span_args(width, stride)) return rc;
-    if (!d_span_offsets || (n_docs > 0 && !d_offsets)) return fail(LDGPU_EINVAL, "device pointer is NULL");
+    if (int rc = check_span_offsets_device(ctx, n_docs, width, stride, d_offsets, d_span_offsets)) return rc;
     if (((uintptr_t)d_utf8 & 3) != 0) return fail(LDGPU_EINVAL, "d_utf8 must be 4-byte aligned");
     if (int rc = check_utf_docs(n_docs)) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -3134,8 +3191,7 @@ extern "C" int ldgpu_span_offsets_utf(ldgpu_ctx* ctx, const uint8_t* utf8, const
 extern "C" int ldgpu_score_topk_utf_device(ldgpu_model* m, const uint8_t* d_utf8, int64_t n_bytes,
                                            const int64_t* d_offsets, int64_t n_docs, int32_t k, int32_t* d_top_labels,
                                            double* d_top_scores, void* stream) {
-    const bool null_ptr = n_docs > 0 && (!d_offsets || !d_top_labels || (n_bytes > 0 && !d_utf8));
-    if (int rc = device_call_begin(m, n_docs, d_utf8, null_ptr, [&] {
+    if (int rc = device_call_begin(m, n_docs, n_docs, d_utf8, n_bytes, {d_offsets, d_top_labels}, [&] {
             if (n_bytes < 0) return fail(LDGPU_EINVAL, "n_bytes < 0");
             if (int r = check_topk(m, k)) return r;
             return check_utf_docs(n_docs);
@@ -3143,31 +3199,16 @@ extern "C" int ldgpu_score_topk_utf_device(ldgpu_model* m, const uint8_t* d_utf8
         return rc;
     if (n_docs == 0) return ok();
     hipStream_t st = (hipStream_t)stream;
-    UtfScratch s;
-    if (int rc = utf_scratch_decode(m, d_utf8, n_bytes, d_offsets, n_docs, &s, st)) return rc;
-    int rc = LDGPU_OK;
-    hipError_t e = hipSuccess;
-    const int64_t chunk = topk_chunk_docs(m->L);
-    for (int64_t d0 = 0; d0 < n_docs && !rc && e == hipSuccess; d0 += chunk) {
-        const int64_t nd = std::min(chunk, n_docs - d0);
-        const size_t score_bytes = sizeof(double) * (size_t)nd * m->L;
-        char* scratch = nullptr;
-        e = hipMallocAsync((void**)&scratch, score_bytes + sizeof(int32_t) * (size_t)nd, st);
-        if (e != hipSuccess) break;
-        rc = score_launch(m, s.dec, n_bytes, s.dec_off + d0, nd, (int32_t*)(scratch + score_bytes), (double*)scratch,
-                          m->d_err, st);
-        if (!rc)
-            e = topk_select(m, (const double*)scratch, nd, k, d_top_labels + d0 * k,
-                            d_top_scores ? d_top_scores + d0 * k : nullptr, st);
-        (void)hipFreeAsync(scratch, st);
-    }
-    if (!rc && e == hipSuccess)
-        e = launch_utf8_topk_labels(s.host, n_docs, k, d_top_labels, d_top_scores, m->ctx->cus, st);
-    (void)hipFreeAsync(s.p, st);
+    UtfBufs u;
+    if (int rc = utf_scratch_bufs(n_docs, n_bytes, &u, st)) return rc;
+    const int rc = utf_topk(m, d_utf8, d_offsets, n_docs, u, k, d_top_labels, d_top_scores, st,
+                            [&](const uint8_t* dec, const int64_t* dec_off) {
+                                return topk_device_chunks(m, dec, n_bytes, dec_off, n_docs, k, d_top_labels,
+                                                          d_top_scores, st);
+                            });
+    (void)hipFreeAsync(u.dec, st);
     if (rc) return rc;
-    HIP_TRY(e);
-    if (int r = check_row_error(m, m->d_err, st)) return r;
-    return ok();
+    return device_call_end(m, st);
 }
 
 extern "C" int ldgpu_score_topk_utf(ldgpu_model* m, const uint8_t* utf8, const int64_t* offsets, int64_t n_docs,
@@ -3176,35 +3217,27 @@ extern "C" int ldgpu_score_topk_utf(ldgpu_model* m, const uint8_t* utf8, const i
                                  [&] { return check_topk(m, k); }))
         return rc;
     if (n_docs == 0) return ok();
-    const ScoreCall call{utf8, offsets, n_docs, nullptr, n_docs,
-                         {{&ScoreStage::top_labels, &ScoreStage::h_labels, out_top_labels, sizeof(int32_t) * k},
-                          {&ScoreStage::top_scores, &ScoreStage::h_scores, out_top_scores, sizeof(double) * k}}};
     auto launch = [&](ScoreStage& st, const PipeChunk& ch, int32_t* d_err) -> int {
-        const int64_t nd = ch.i1 - ch.i0, nb = ch.hi - ch.lo;
-        HIP_TRY(st.labels.ensure(sizeof(int32_t) * nd));
-        HIP_TRY(st.scores.ensure(sizeof(double) * nd * m->L));
-        if (int r = stage_decode(m, st, nd, nb)) return r;
-        if (int r = score_launch(m, (const uint8_t*)st.dec.p, nb, (const int64_t*)st.dec_offsets.p, nd,
-                                 (int32_t*)st.labels.p, (double*)st.scores.p, d_err, st.stream))
-            return r;
-        double* top_scores = out_top_scores ? (double*)st.top_scores.p : nullptr;
-        HIP_TRY(topk_select(m, (const double*)st.scores.p, nd, k, (int32_t*)st.top_labels.p, top_scores, st.stream));
-        HIP_TRY(launch_utf8_topk_labels((const uint8_t*)st.dec_host.p, nd, k, (int32_t*)st.top_labels.p, top_scores,
-                                        m->ctx->cus, st.stream));
-        return LDGPU_OK;
+        const int64_t nd = ch.i1 - ch.i0;
+        UtfBufs u;
+        if (int r = topk_stage_scratch(m, st, ch)) return r;
+        if (int r = utf_stage_bufs(st, nd, ch.hi - ch.lo, &u)) return r;
+        return utf_topk(m, (const uint8_t*)st.bytes.p, (const int64_t*)st.offsets.p, nd, u, k,
+                        (int32_t*)st.top_labels.p, out_top_scores ? (double*)st.top_scores.p : nullptr, st.stream,
+                        [&](const uint8_t* dec, const int64_t* dec_off) {
+                            return topk_stage_chunk(m, st, ch, dec, dec_off, k, out_top_scores != nullptr, d_err);
+                        });
     };
     const int64_t max_docs = std::min(score_chunk_docs(), topk_chunk_docs(m->L));
-    return with_pipe(m, [&](ScorePipe* pp) {
-        return run_score_pipe(m, pp, call, doc_chunks(offsets, n_docs, max_docs), launch);
-    });
+    return host_call(m, topk_call(utf8, offsets, n_docs, k, out_top_labels, out_top_scores),
+                     doc_chunks(offsets, n_docs, max_docs), launch);
 }
 
 extern "C" int ldgpu_score_spans_utf_device(ldgpu_model* m, const uint8_t* d_utf8, int64_t n_bytes,
                                             const int64_t* d_offsets, int64_t n_docs, int32_t width, int32_t stride,
                                             const int64_t* d_span_offsets, int64_t n_spans, int32_t* d_labels,
                                             double* d_scores, int64_t* d_starts, void* stream) {
-    const bool null_ptr = n_spans > 0 && (!d_offsets || !d_span_offsets || !d_labels || (n_bytes > 0 && !d_utf8));
-    if (int rc = device_call_begin(m, n_docs, d_utf8, null_ptr, [&] {
+    if (int rc = device_call_begin(m, n_docs, n_spans, d_utf8, n_bytes, {d_offsets, d_span_offsets, d_labels}, [&] {
             if (n_bytes < 0) return fail(LDGPU_EINVAL, "n_bytes < 0");
             if (n_spans < 0) return fail(LDGPU_EINVAL, "n_spans < 0");
             if (int r = check_span_args(width, stride)) return r;
@@ -3213,24 +3246,14 @@ extern "C" int ldgpu_score_spans_utf_device(ldgpu_model* m, const uint8_t* d_utf
         return rc;
     if (n_spans == 0) return ok();
     hipStream_t st = (hipStream_t)stream;
-    UtfScratch s;
-    if (int rc = utf_scratch_decode(m, d_utf8, n_bytes, d_offsets, n_docs, &s, st)) return rc;
-    SpanParams sp{};
-    sp.bytes = s.dec;
-    sp.n_bytes = n_bytes;
-    sp.offsets = s.dec_off;
-    sp.n_docs = n_docs;
-    sp.span_offsets = d_span_offsets;
-    sp.width = width;
-    sp.stride = stride;
-    int rc = span_chunks(m, sp, n_spans, span_chunk_spans(width), d_labels, d_scores, m->d_err, st);
-    if (!rc)
-        rc = utf_span_finish(m, d_utf8, d_offsets, n_docs, s.host, d_span_offsets, n_spans, stride, d_labels, d_starts,
-                             st);
-    (void)hipFreeAsync(s.p, st);
-    if (rc) return rc;
-    if (int r = check_row_error(m, m->d_err, st)) return r;
-    return ok();
+    auto twin = [&](const uint8_t* dec, const int64_t* dec_off) {
+        const SpanParams sp = span_corpus(dec, n_bytes, dec_off, n_docs, d_span_offsets, width, stride);
+        return span_chunks(m, sp, n_spans, span_chunk_spans(width), d_labels, d_scores, m->d_err, st);
+    };
+    if (int rc = device_utf_spans(m, d_utf8, n_bytes, d_offsets, n_docs, d_span_offsets, n_spans, stride, d_labels,
+                                  d_starts, st, twin))
+        return rc;
+    return device_call_end(m, st);
 }
 
 extern "C" int ldgpu_score_spans_utf(ldgpu_model* m, const uint8_t* utf8, const int64_t* offsets, int64_t n_docs,
@@ -3241,44 +3264,23 @@ extern "C" int ldgpu_score_spans_utf(ldgpu_model* m, const uint8_t* utf8, const 
         return rc;
     if (n_docs == 0) return ok();
     if (int rc = check_span_offsets(span_offsets, n_docs)) return rc;
-    const int64_t n_spans = span_offsets[n_docs];
-    const ScoreCall call{utf8, offsets, n_docs, span_offsets, n_spans,
-                         {{&ScoreStage::labels, &ScoreStage::h_labels, out_labels, sizeof(int32_t)},
-                          {&ScoreStage::scores, &ScoreStage::h_scores, out_scores, sizeof(double) * m->L},
-                          {&ScoreStage::starts, &ScoreStage::h_starts, out_starts, sizeof(int64_t)}}};
-    // (with scores the stage's score buffer bounds a chunk too, as in the span form)
-    int64_t budget = span_chunk_spans(width);
-    if (out_scores) budget = std::min(budget, topk_chunk_docs(m->L));
+    const ScoreCall call = label_call(m, utf8, offsets, n_docs, span_offsets, span_offsets[n_docs], out_labels,
+                                      out_scores, out_starts);
+    const int64_t budget = span_budget(m, width, out_scores != nullptr);
     auto launch = [&](ScoreStage& st, const PipeChunk& ch, int32_t* d_err) -> int {
-        const int64_t nd = ch.n_docs, nb = ch.hi - ch.lo, n = ch.i1 - ch.i0;
-        if (int r = stage_decode(m, st, nd, nb)) return r;
-        const int64_t* soff = (const int64_t*)st.offsets.p + nd + 1;
-        SpanParams sp{};
-        sp.bytes = (const uint8_t*)st.dec.p;
-        sp.n_bytes = nb;
-        sp.offsets = (const int64_t*)st.dec_offsets.p;
-        sp.n_docs = nd;
-        sp.span_offsets = soff;
-        sp.width = width;
-        sp.stride = stride;
-        if (int r = span_chunks(m, sp, n, budget, (int32_t*)st.labels.p, out_scores ? (double*)st.scores.p : nullptr,
-                                d_err, st.stream))
-            return r;
-        return utf_span_finish(m, (const uint8_t*)st.bytes.p, (const int64_t*)st.offsets.p, nd,
-                               (const uint8_t*)st.dec_host.p, soff, n, stride, (int32_t*)st.labels.p,
-                               out_starts ? (int64_t*)st.starts.p : nullptr, st.stream);
+        auto twin = [&](const uint8_t* dec, const int64_t* dec_off) {
+            return stage_spans(m, st, ch, dec, dec_off, width, stride, budget, out_scores != nullptr, d_err);
+        };
+        return stage_utf_spans(m, st, ch, stride, out_starts != nullptr, twin);
     };
-    return with_pipe(m, [&](ScorePipe* pp) {
-        return run_score_pipe(m, pp, call, span_doc_chunks(offsets, span_offsets, n_docs, budget), launch);
-    });
+    return host_call(m, call, span_doc_chunks(offsets, span_offsets, n_docs, budget), launch);
 }
 
 extern "C" int ldgpu_score_segments_utf_device(ldgpu_model* m, const uint8_t* d_utf8, int64_t n_bytes,
                                                const int64_t* d_offsets, int64_t n_docs, int32_t width,
                                                int32_t stride, double penalty, const int64_t* d_span_offsets,
                                                int64_t n_spans, int32_t* d_labels, int64_t* d_starts, void* stream) {
-    const bool null_ptr = n_spans > 0 && (!d_offsets || !d_span_offsets || !d_labels || (n_bytes > 0 && !d_utf8));
-    if (int rc = device_call_begin(m, n_docs, d_utf8, null_ptr, [&] {
+    if (int rc = device_call_begin(m, n_docs, n_spans, d_utf8, n_bytes, {d_offsets, d_span_offsets, d_labels}, [&] {
             if (n_bytes < 0) return fail(LDGPU_EINVAL, "n_bytes < 0");
             if (n_spans < 0) return fail(LDGPU_EINVAL, "n_spans < 0");
             if (int r = check_span_args(width, stride)) return r;
@@ -3288,24 +3290,14 @@ extern "C" int ldgpu_score_segments_utf_device(ldgpu_model* m, const uint8_t* d_
         return rc;
     if (n_spans == 0) return ok();
     hipStream_t st = (hipStream_t)stream;
-    UtfScratch s;
-    if (int rc = utf_scratch_decode(m, d_utf8, n_bytes, d_offsets, n_docs, &s, st)) return rc;
-    SpanParams sp{};
-    sp.bytes = s.dec;
-    sp.n_bytes = n_bytes;
-    sp.offsets = s.dec_off;
-    sp.n_docs = n_docs;
-    sp.span_offsets = d_span_offsets;
-    sp.width = width;
-    sp.stride = stride;
-    int rc = segments_launch(m, sp, penalty, n_spans, d_labels, m->d_err, st);
-    if (!rc)
-        rc = utf_span_finish(m, d_utf8, d_offsets, n_docs, s.host, d_span_offsets, n_spans, stride, d_labels, d_starts,
-                             st);
-    (void)hipFreeAsync(s.p, st);
-    if (rc) return rc;
-    if (int r = check_row_error(m, m->d_err, st)) return r;
-    return ok();
+    auto twin = [&](const uint8_t* dec, const int64_t* dec_off) {
+        const SpanParams sp = span_corpus(dec, n_bytes, dec_off, n_docs, d_span_offsets, width, stride);
+        return segments_launch(m, sp, penalty, n_spans, d_labels, m->d_err, st);
+    };
+    if (int rc = device_utf_spans(m, d_utf8, n_bytes, d_offsets, n_docs, d_span_offsets, n_spans, stride, d_labels,
+                                  d_starts, st, twin))
+        return rc;
+    return device_call_end(m, st);
 }
 
 extern "C" int ldgpu_score_segments_utf(ldgpu_model* m, const uint8_t* utf8, const int64_t* offsets, int64_t n_docs,
@@ -3318,32 +3310,15 @@ extern "C" int ldgpu_score_segments_utf(ldgpu_model* m, const uint8_t* utf8, con
         return rc;
     if (n_docs == 0) return ok();
     if (int rc = check_span_offsets(span_offsets, n_docs)) return rc;
-    const int64_t n_spans = span_offsets[n_docs];
-    const ScoreCall call{utf8, offsets, n_docs, span_offsets, n_spans,
-                         {{&ScoreStage::labels, &ScoreStage::h_labels, out_labels, sizeof(int32_t)},
-                          {&ScoreStage::scores, &ScoreStage::h_scores, nullptr, 0},
-                          {&ScoreStage::starts, &ScoreStage::h_starts, out_starts, sizeof(int64_t)}}};
+    const ScoreCall call = label_call(m, utf8, offsets, n_docs, span_offsets, span_offsets[n_docs], out_labels, nullptr,
+                                      out_starts);
     auto launch = [&](ScoreStage& st, const PipeChunk& ch, int32_t* d_err) -> int {
-        const int64_t nd = ch.n_docs, nb = ch.hi - ch.lo, n = ch.i1 - ch.i0;
-        if (int r = stage_decode(m, st, nd, nb)) return r;
-        const int64_t* soff = (const int64_t*)st.offsets.p + nd + 1;
-        SpanParams sp{};
-        sp.bytes = (const uint8_t*)st.dec.p;
-        sp.n_bytes = nb;
-        sp.offsets = (const int64_t*)st.dec_offsets.p;
-        sp.n_docs = nd;
-        sp.span_offsets = soff;
-        sp.width = width;
-        sp.stride = stride;
-        if (int r = segments_launch(m, sp, penalty, n, (int32_t*)st.labels.p, d_err, st.stream)) return r;
-        return utf_span_finish(m, (const uint8_t*)st.bytes.p, (const int64_t*)st.offsets.p, nd,
-                               (const uint8_t*)st.dec_host.p, soff, n, stride, (int32_t*)st.labels.p,
-                               out_starts ? (int64_t*)st.starts.p : nullptr, st.stream);
+        auto twin = [&](const uint8_t* dec, const int64_t* dec_off) {
+            return stage_segments(m, st, ch, dec, dec_off, width, stride, penalty, d_err);
+        };
+        return stage_utf_spans(m, st, ch, stride, out_starts != nullptr, twin);
     };
-    return with_pipe(m, [&](ScorePipe* pp) {
-        return run_score_pipe(m, pp, call, span_doc_chunks(offsets, span_offsets, n_docs, span_chunk_spans(width)),
-                              launch);
-    });
+    return host_call(m, call, span_doc_chunks(offsets, span_offsets, n_docs, span_chunk_spans(width)), launch);
 }
 
 // ---------------------------------------------------------------------- FIT

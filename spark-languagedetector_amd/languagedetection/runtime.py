@@ -19,6 +19,14 @@ def _grams(gram_lengths: Sequence[int]) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(list(gram_lengths), dtype=np.int32))
 
 
+def _out(out: Optional[np.ndarray], shape: Tuple[int, ...], dtype) -> np.ndarray:
+    """An output array: the caller's `out`, which must fit, or a new one."""
+    if out is None:
+        return np.zeros(shape, dtype=dtype)
+    assert out.dtype == dtype and out.shape == shape and out.flags.c_contiguous
+    return out
+
+
 class _Owner:
     lib = None
 
@@ -117,21 +125,37 @@ class DeviceModel(_Owner):
                 "filter_bits": vals[2].value, "device_bytes": vals[3].value,
                 "layout": sorted(k for k, b in _lib.LAYOUT_FLAGS.items() if flags.value & b)}
 
+    def _score(self, fn, data, offsets, want_scores, out):
+        """score / score_utf8 through the C entry point `fn`."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = len(offsets) - 1
+        labels = _out(out, (max(n, 0),), np.int32)
+        scores = np.zeros((max(n, 0), self.L), dtype=np.float64) if want_scores else None
+        self._check(fn(self.h, _ptr(data), _ptr(offsets), n, _ptr(labels), _ptr(scores)))
+        return labels, scores
+
+    def _score_topk(self, fn, data, offsets, k, want_scores, out_labels, out_scores):
+        """score_topk / score_topk_utf8 through the C entry point `fn`."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n, k = max(len(offsets) - 1, 0), int(k)
+        shape = (n, max(k, 0))
+        labels = _out(out_labels, shape, np.int32)
+        scores = _out(out_scores, shape, np.float64) if want_scores else None
+        self._check(fn(self.h, _ptr(data), _ptr(offsets), len(offsets) - 1, k, _ptr(labels), _ptr(scores)))
+        return labels, scores
+
+    def _device_call(self, fn, stream: Optional[int], *args) -> None:
+        """fn(*args, stream) on device pointers given as integers (0 = NULL:
+        the entry points take them as void*); `stream` None = the context's."""
+        self._check(fn(*args, self.stream() if stream is None else stream))
+
     def score(self, data: np.ndarray, offsets: np.ndarray, want_scores: bool = False,
               out: Optional[np.ndarray] = None) -> Tuple[np.ndarray, Optional[np.ndarray]]:
         """Host buffers -> (labels int32[n], scores fp64[n, L] or None);
         `out` (e.g. a PinnedArray's array) receives the labels."""
-        data = np.ascontiguousarray(data, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        n = len(offsets) - 1
-        if out is not None:
-            labels = out
-            assert labels.dtype == np.int32 and labels.shape == (max(n, 0),) and labels.flags.c_contiguous
-        else:
-            labels = np.zeros(max(n, 0), dtype=np.int32)
-        scores = np.zeros((max(n, 0), self.L), dtype=np.float64) if want_scores else None
-        self._check(self.lib.ldgpu_score(self.h, _ptr(data), _ptr(offsets), n, _ptr(labels), _ptr(scores)))
-        return labels, scores
+        return self._score(self.lib.ldgpu_score, data, offsets, want_scores, out)
 
     def stream(self) -> int:
         """The context's hipStream_t."""
@@ -142,11 +166,8 @@ class DeviceModel(_Owner):
         """Device pointers (e.g. torch tensors' data_ptr()) -> labels in place,
         async on `stream` (a hipStream_t; 0 = the null stream, None = the
         context's stream)."""
-        st = self.stream() if stream is None else stream
-        self._check(self.lib.ldgpu_score_device(self.h, ctypes.c_void_p(d_bytes), n_bytes, ctypes.c_void_p(d_offsets),
-                                               n_docs, ctypes.c_void_p(d_labels),
-                                               ctypes.c_void_p(d_scores) if d_scores else None,
-                                               ctypes.c_void_p(st) if st else None))
+        self._device_call(self.lib.ldgpu_score_device, stream, self.h, d_bytes, n_bytes, d_offsets, n_docs, d_labels,
+                          d_scores)
 
     def score_topk(self, data: np.ndarray, offsets: np.ndarray, k: int, want_scores: bool = True,
                    out_labels: Optional[np.ndarray] = None, out_scores: Optional[np.ndarray] = None
@@ -155,28 +176,14 @@ class DeviceModel(_Owner):
         scores fp64[n, k] or None), selected on the device (ldgpu_score_topk;
         the order: languagedetection.topk).  `out_labels` / `out_scores` (e.g.
         PinnedArray arrays) receive the results."""
-        data = np.ascontiguousarray(data, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        n, k = max(len(offsets) - 1, 0), int(k)
-        shape = (n, max(k, 0))
-        labels = np.zeros(shape, dtype=np.int32) if out_labels is None else out_labels
-        scores = (np.zeros(shape, dtype=np.float64) if out_scores is None else out_scores) if want_scores else None
-        assert labels.dtype == np.int32 and labels.shape == shape and labels.flags.c_contiguous
-        assert scores is None or (scores.dtype == np.float64 and scores.shape == shape and scores.flags.c_contiguous)
-        self._check(self.lib.ldgpu_score_topk(self.h, _ptr(data), _ptr(offsets), len(offsets) - 1, k, _ptr(labels),
-                                              _ptr(scores)))
-        return labels, scores
+        return self._score_topk(self.lib.ldgpu_score_topk, data, offsets, k, want_scores, out_labels, out_scores)
 
     def score_topk_device(self, d_bytes: int, n_bytes: int, d_offsets: int, n_docs: int, k: int, d_top_labels: int,
                           d_top_scores: int = 0, stream: Optional[int] = None) -> None:
         """Device pointers -> the [n_docs, k] labels (and scores) in place,
         async on `stream` as score_device (ldgpu_score_topk_device)."""
-        st = self.stream() if stream is None else stream
-        self._check(self.lib.ldgpu_score_topk_device(self.h, ctypes.c_void_p(d_bytes), n_bytes,
-                                                     ctypes.c_void_p(d_offsets), n_docs, int(k),
-                                                     ctypes.c_void_p(d_top_labels),
-                                                     ctypes.c_void_p(d_top_scores) if d_top_scores else None,
-                                                     ctypes.c_void_p(st) if st else None))
+        self._device_call(self.lib.ldgpu_score_topk_device, stream, self.h, d_bytes, n_bytes, d_offsets, n_docs,
+                          int(k), d_top_labels, d_top_scores)
 
     # UTF-8 documents (an addition; the rule: languagedetection.utf8)
     def score_utf8(self, data: np.ndarray, offsets: np.ndarray, want_scores: bool = False,
@@ -185,27 +192,14 @@ class DeviceModel(_Owner):
         L] or None) as score gives for their SCORE encoding, decoded on the
         device (ldgpu_score_utf8); an ill-formed document gets label -1 and an
         empty document's score row.  `out` receives the labels."""
-        data = np.ascontiguousarray(data, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        n = len(offsets) - 1
-        if out is not None:
-            labels = out
-            assert labels.dtype == np.int32 and labels.shape == (max(n, 0),) and labels.flags.c_contiguous
-        else:
-            labels = np.zeros(max(n, 0), dtype=np.int32)
-        scores = np.zeros((max(n, 0), self.L), dtype=np.float64) if want_scores else None
-        self._check(self.lib.ldgpu_score_utf8(self.h, _ptr(data), _ptr(offsets), n, _ptr(labels), _ptr(scores)))
-        return labels, scores
+        return self._score(self.lib.ldgpu_score_utf8, data, offsets, want_scores, out)
 
     def score_utf8_device(self, d_utf8: int, n_bytes: int, d_offsets: int, n_docs: int, d_labels: int,
                           d_scores: int = 0, stream: Optional[int] = None) -> None:
         """Device pointers to UTF-8 documents -> labels (and scores) in place,
         async on `stream` as score_device (ldgpu_score_utf8_device)."""
-        st = self.stream() if stream is None else stream
-        self._check(self.lib.ldgpu_score_utf8_device(self.h, ctypes.c_void_p(d_utf8), n_bytes,
-                                                     ctypes.c_void_p(d_offsets), n_docs, ctypes.c_void_p(d_labels),
-                                                     ctypes.c_void_p(d_scores) if d_scores else None,
-                                                     ctypes.c_void_p(st) if st else None))
+        self._device_call(self.lib.ldgpu_score_utf8_device, stream, self.h, d_utf8, n_bytes, d_offsets, n_docs,
+                          d_labels, d_scores)
 
     # Span scoring (an addition; the rule: languagedetection.spans)
     def span_offsets(self, offsets: np.ndarray, width: int, stride: int) -> np.ndarray:
@@ -219,10 +213,8 @@ class DeviceModel(_Owner):
                             stream: Optional[int] = None) -> None:
         """Device pointers -> d_span_offsets int64[n_docs + 1] in place, async
         on `stream` as score_device (ldgpu_span_offsets_device)."""
-        st = self.stream() if stream is None else stream
-        self._check(self.lib.ldgpu_span_offsets_device(self.ctx, ctypes.c_void_p(d_offsets), n_docs, int(width),
-                                                       int(stride), ctypes.c_void_p(d_span_offsets),
-                                                       ctypes.c_void_p(st) if st else None))
+        self._device_call(self.lib.ldgpu_span_offsets_device, stream, self.ctx, d_offsets, n_docs, int(width),
+                          int(stride), d_span_offsets)
 
     def score_spans(self, data: np.ndarray, offsets: np.ndarray, width: int, stride: int, want_scores: bool = False,
                     out_labels: Optional[np.ndarray] = None, out_scores: Optional[np.ndarray] = None
@@ -236,11 +228,8 @@ class DeviceModel(_Owner):
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         soff = self.span_offsets(offsets, width, stride)
         n = int(soff[-1])
-        labels = np.zeros(n, dtype=np.int32) if out_labels is None else out_labels
-        scores = (np.zeros((n, self.L), dtype=np.float64) if out_scores is None else out_scores) if want_scores else None
-        assert labels.dtype == np.int32 and labels.shape == (n,) and labels.flags.c_contiguous
-        assert scores is None or (scores.dtype == np.float64 and scores.shape == (n, self.L)
-                                  and scores.flags.c_contiguous)
+        labels = _out(out_labels, (n,), np.int32)
+        scores = _out(out_scores, (n, self.L), np.float64) if want_scores else None
         self._check(self.lib.ldgpu_score_spans(self.h, _ptr(data), _ptr(offsets), len(offsets) - 1, int(width),
                                                int(stride), _ptr(labels), _ptr(scores)))
         return labels, scores, soff
@@ -250,13 +239,8 @@ class DeviceModel(_Owner):
                            stream: Optional[int] = None) -> None:
         """Device pointers -> the [n_spans] labels (and [n_spans, L] scores) in
         place, async on `stream` as score_device (ldgpu_score_spans_device)."""
-        st = self.stream() if stream is None else stream
-        self._check(self.lib.ldgpu_score_spans_device(self.h, ctypes.c_void_p(d_bytes), n_bytes,
-                                                      ctypes.c_void_p(d_offsets), n_docs, int(width), int(stride),
-                                                      ctypes.c_void_p(d_span_offsets), n_spans,
-                                                      ctypes.c_void_p(d_labels),
-                                                      ctypes.c_void_p(d_scores) if d_scores else None,
-                                                      ctypes.c_void_p(st) if st else None))
+        self._device_call(self.lib.ldgpu_score_spans_device, stream, self.h, d_bytes, n_bytes, d_offsets, n_docs,
+                          int(width), int(stride), d_span_offsets, n_spans, d_labels, d_scores)
 
     # Smoothed span labels (an addition; the rule: languagedetection.segments)
     def score_segments(self, data: np.ndarray, offsets: np.ndarray, width: int, stride: int, penalty: float,
@@ -269,9 +253,7 @@ class DeviceModel(_Owner):
         data = np.ascontiguousarray(data, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         soff = self.span_offsets(offsets, width, stride)
-        n = int(soff[-1])
-        labels = np.zeros(n, dtype=np.int32) if out_labels is None else out_labels
-        assert labels.dtype == np.int32 and labels.shape == (n,) and labels.flags.c_contiguous
+        labels = _out(out_labels, (int(soff[-1]),), np.int32)
         self._check(self.lib.ldgpu_score_segments(self.h, _ptr(data), _ptr(offsets), len(offsets) - 1, int(width),
                                                   int(stride), float(penalty), _ptr(labels)))
         return labels, soff
@@ -281,13 +263,8 @@ class DeviceModel(_Owner):
                               stream: Optional[int] = None) -> None:
         """Device pointers -> the [n_spans] smoothed labels in place, async on
         `stream` as score_device (ldgpu_score_segments_device)."""
-        st = self.stream() if stream is None else stream
-        self._check(self.lib.ldgpu_score_segments_device(self.h, ctypes.c_void_p(d_bytes), n_bytes,
-                                                         ctypes.c_void_p(d_offsets), n_docs, int(width), int(stride),
-                                                         float(penalty), ctypes.c_void_p(d_span_offsets), n_spans,
-                                                         ctypes.c_void_p(d_labels),
-                                                         ctypes.c_void_p(st) if st else None))
-
+        self._device_call(self.lib.ldgpu_score_segments_device, stream, self.h, d_bytes, n_bytes, d_offsets, n_docs,
+                          int(width), int(stride), float(penalty), d_span_offsets, n_spans, d_labels)
 
     # Top-k, spans and segments of UTF-8 documents (an addition; the rule:
     # languagedetection.utf8)
@@ -310,12 +287,8 @@ class DeviceModel(_Owner):
         """Device pointers -> d_span_offsets int64[n_docs + 1] (and d_units
         int64[n_docs]) in place, async on `stream` as score_device
         (ldgpu_span_offsets_utf_device)."""
-        st = self.stream() if stream is None else stream
-        self._check(self.lib.ldgpu_span_offsets_utf_device(self.ctx, ctypes.c_void_p(d_utf8),
-                                                           ctypes.c_void_p(d_offsets), n_docs, int(width), int(stride),
-                                                           ctypes.c_void_p(d_span_offsets),
-                                                           ctypes.c_void_p(d_units) if d_units else None,
-                                                           ctypes.c_void_p(st) if st else None))
+        self._device_call(self.lib.ldgpu_span_offsets_utf_device, stream, self.ctx, d_utf8, d_offsets, n_docs,
+                          int(width), int(stride), d_span_offsets, d_units)
 
     def score_topk_utf8(self, data: np.ndarray, offsets: np.ndarray, k: int, want_scores: bool = True,
                         out_labels: Optional[np.ndarray] = None, out_scores: Optional[np.ndarray] = None
@@ -323,28 +296,23 @@ class DeviceModel(_Owner):
         """score_topk over host buffers of UTF-8 documents, decoded on the
         device (ldgpu_score_topk_utf); an ill-formed document's row is -1 in
         every label and 0.0 in every score."""
-        data = np.ascontiguousarray(data, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        n, k = max(len(offsets) - 1, 0), int(k)
-        shape = (n, max(k, 0))
-        labels = np.zeros(shape, dtype=np.int32) if out_labels is None else out_labels
-        scores = (np.zeros(shape, dtype=np.float64) if out_scores is None else out_scores) if want_scores else None
-        assert labels.dtype == np.int32 and labels.shape == shape and labels.flags.c_contiguous
-        assert scores is None or (scores.dtype == np.float64 and scores.shape == shape and scores.flags.c_contiguous)
-        self._check(self.lib.ldgpu_score_topk_utf(self.h, _ptr(data), _ptr(offsets), len(offsets) - 1, k, _ptr(labels),
-                                                  _ptr(scores)))
-        return labels, scores
+        return self._score_topk(self.lib.ldgpu_score_topk_utf, data, offsets, k, want_scores, out_labels, out_scores)
 
     def score_topk_utf8_device(self, d_utf8: int, n_bytes: int, d_offsets: int, n_docs: int, k: int,
                                d_top_labels: int, d_top_scores: int = 0, stream: Optional[int] = None) -> None:
         """Device pointers to UTF-8 documents -> the [n_docs, k] labels (and
         scores) in place, async on `stream` (ldgpu_score_topk_utf_device)."""
-        st = self.stream() if stream is None else stream
-        self._check(self.lib.ldgpu_score_topk_utf_device(self.h, ctypes.c_void_p(d_utf8), n_bytes,
-                                                         ctypes.c_void_p(d_offsets), n_docs, int(k),
-                                                         ctypes.c_void_p(d_top_labels),
-                                                         ctypes.c_void_p(d_top_scores) if d_top_scores else None,
-                                                         ctypes.c_void_p(st) if st else None))
+        self._device_call(self.lib.ldgpu_score_topk_utf_device, stream, self.h, d_utf8, n_bytes, d_offsets, n_docs,
+                          int(k), d_top_labels, d_top_scores)
+
+    def _utf8_spans(self, data, offsets, width, stride, span_offsets):
+        """(data, offsets, span offsets) of a UTF-8 span / segment call:
+        `span_offsets` is span_offsets_utf8's output when the caller has it."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        soff = (self.span_offsets_utf8(data, offsets, width, stride)[0] if span_offsets is None
+                else np.ascontiguousarray(span_offsets, dtype=np.int64))
+        return data, offsets, soff
 
     def score_spans_utf8(self, data: np.ndarray, offsets: np.ndarray, width: int, stride: int,
                          want_scores: bool = False, want_starts: bool = True,
@@ -358,18 +326,11 @@ class DeviceModel(_Owner):
         document's single span gets -1 (ldgpu_score_spans_utf).  `span_offsets`
         is span_offsets_utf8's output when the caller has it already; the
         `out_*` arrays (e.g. PinnedArray arrays) receive the results."""
-        data = np.ascontiguousarray(data, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        soff = (self.span_offsets_utf8(data, offsets, width, stride)[0] if span_offsets is None
-                else np.ascontiguousarray(span_offsets, dtype=np.int64))
+        data, offsets, soff = self._utf8_spans(data, offsets, width, stride, span_offsets)
         n = int(soff[-1])
-        labels = np.zeros(n, dtype=np.int32) if out_labels is None else out_labels
-        scores = (np.zeros((n, self.L), dtype=np.float64) if out_scores is None else out_scores) if want_scores else None
-        starts = (np.zeros(n, dtype=np.int64) if out_starts is None else out_starts) if want_starts else None
-        assert labels.dtype == np.int32 and labels.shape == (n,) and labels.flags.c_contiguous
-        assert scores is None or (scores.dtype == np.float64 and scores.shape == (n, self.L)
-                                  and scores.flags.c_contiguous)
-        assert starts is None or (starts.dtype == np.int64 and starts.shape == (n,) and starts.flags.c_contiguous)
+        labels = _out(out_labels, (n,), np.int32)
+        scores = _out(out_scores, (n, self.L), np.float64) if want_scores else None
+        starts = _out(out_starts, (n,), np.int64) if want_starts else None
         self._check(self.lib.ldgpu_score_spans_utf(self.h, _ptr(data), _ptr(offsets), len(offsets) - 1, int(width),
                                                    int(stride), _ptr(soff), _ptr(labels), _ptr(scores), _ptr(starts)))
         return labels, scores, starts, soff
@@ -380,14 +341,8 @@ class DeviceModel(_Owner):
         """Device pointers to UTF-8 documents -> the [n_spans] labels (and
         [n_spans, L] scores, [n_spans] starts) in place, async on `stream`
         (ldgpu_score_spans_utf_device)."""
-        st = self.stream() if stream is None else stream
-        self._check(self.lib.ldgpu_score_spans_utf_device(self.h, ctypes.c_void_p(d_utf8), n_bytes,
-                                                          ctypes.c_void_p(d_offsets), n_docs, int(width), int(stride),
-                                                          ctypes.c_void_p(d_span_offsets), n_spans,
-                                                          ctypes.c_void_p(d_labels),
-                                                          ctypes.c_void_p(d_scores) if d_scores else None,
-                                                          ctypes.c_void_p(d_starts) if d_starts else None,
-                                                          ctypes.c_void_p(st) if st else None))
+        self._device_call(self.lib.ldgpu_score_spans_utf_device, stream, self.h, d_utf8, n_bytes, d_offsets, n_docs,
+                          int(width), int(stride), d_span_offsets, n_spans, d_labels, d_scores, d_starts)
 
     def score_segments_utf8(self, data: np.ndarray, offsets: np.ndarray, width: int, stride: int, penalty: float,
                             want_starts: bool = True, span_offsets: Optional[np.ndarray] = None,
@@ -397,15 +352,10 @@ class DeviceModel(_Owner):
         int64[n_spans] or None, span_offsets int64[n_docs + 1]): score_segments
         of the documents' SCORE encoding with the spans' byte starts; an
         ill-formed document's single span gets -1 (ldgpu_score_segments_utf)."""
-        data = np.ascontiguousarray(data, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        soff = (self.span_offsets_utf8(data, offsets, width, stride)[0] if span_offsets is None
-                else np.ascontiguousarray(span_offsets, dtype=np.int64))
+        data, offsets, soff = self._utf8_spans(data, offsets, width, stride, span_offsets)
         n = int(soff[-1])
-        labels = np.zeros(n, dtype=np.int32) if out_labels is None else out_labels
-        starts = (np.zeros(n, dtype=np.int64) if out_starts is None else out_starts) if want_starts else None
-        assert labels.dtype == np.int32 and labels.shape == (n,) and labels.flags.c_contiguous
-        assert starts is None or (starts.dtype == np.int64 and starts.shape == (n,) and starts.flags.c_contiguous)
+        labels = _out(out_labels, (n,), np.int32)
+        starts = _out(out_starts, (n,), np.int64) if want_starts else None
         self._check(self.lib.ldgpu_score_segments_utf(self.h, _ptr(data), _ptr(offsets), len(offsets) - 1, int(width),
                                                       int(stride), float(penalty), _ptr(soff), _ptr(labels),
                                                       _ptr(starts)))
@@ -416,14 +366,8 @@ class DeviceModel(_Owner):
                                    d_starts: int = 0, stream: Optional[int] = None) -> None:
         """Device pointers to UTF-8 documents -> the [n_spans] smoothed labels
         (and starts) in place, async on `stream` (ldgpu_score_segments_utf_device)."""
-        st = self.stream() if stream is None else stream
-        self._check(self.lib.ldgpu_score_segments_utf_device(self.h, ctypes.c_void_p(d_utf8), n_bytes,
-                                                             ctypes.c_void_p(d_offsets), n_docs, int(width),
-                                                             int(stride), float(penalty),
-                                                             ctypes.c_void_p(d_span_offsets), n_spans,
-                                                             ctypes.c_void_p(d_labels),
-                                                             ctypes.c_void_p(d_starts) if d_starts else None,
-                                                             ctypes.c_void_p(st) if st else None))
+        self._device_call(self.lib.ldgpu_score_segments_utf_device, stream, self.h, d_utf8, n_bytes, d_offsets,
+                          n_docs, int(width), int(stride), float(penalty), d_span_offsets, n_spans, d_labels, d_starts)
 
 
 class DeviceCounts(_Owner):

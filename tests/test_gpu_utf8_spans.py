@@ -234,8 +234,9 @@ def test_topk_parity(kind):
 @pytest.mark.parametrize("kind", ["count", "dense"])
 def test_chunk_cuts(kind, monkeypatch):
     """The diagnostics library with chunks of a few documents and a few spans:
-    outputs identical to the uncut call; one document has more spans than the
-    budget."""
+    outputs of the host and the device forms identical to the uncut host
+    call; one document has more spans than the budget."""
+    import torch
     width, stride = 3, 2
     _, docs, _, _ = corpus(kind)
     docs = docs[:24]
@@ -259,6 +260,41 @@ def test_chunk_cuts(kind, monkeypatch):
         got = md.score_topk_utf8(data, off, 3)
         assert np.array_equal(got[0], want_top[0]) and np.array_equal(bits(got[1]), bits(want_top[1]))
     monkeypatch.delenv("LDGPU_SCORE_CHUNK_DOCS")
+    # the device forms under the same cuts
+    dev = torch.device("cuda", 0)
+    L, n, ns = TABLES[kind][0], len(docs), int(soff[-1])
+    stream = torch.cuda.Stream(dev)
+    with torch.cuda.stream(stream):
+        st = stream.cuda_stream
+        d_data, d_off, d_soff = (torch.from_numpy(np.array(a)).to(dev) for a in (data, off, soff))
+        for budget in (1, 5, 64):
+            monkeypatch.setenv("LDGPU_SPAN_CHUNK_SPANS", str(budget))
+            d_lab = torch.full((ns,), -7, dtype=torch.int32, device=dev)
+            d_sc = torch.full((ns, L), -7.0, dtype=torch.float64, device=dev)
+            d_sta = torch.full((ns,), -7, dtype=torch.int64, device=dev)
+            md.score_spans_utf8_device(d_data.data_ptr(), len(data), d_off.data_ptr(), n, width, stride,
+                                       d_soff.data_ptr(), ns, d_lab.data_ptr(), d_sc.data_ptr(), d_sta.data_ptr(),
+                                       stream=st)
+            d_seg = torch.full((ns,), -7, dtype=torch.int32, device=dev)
+            d_seg_sta = torch.full((ns,), -7, dtype=torch.int64, device=dev)
+            md.score_segments_utf8_device(d_data.data_ptr(), len(data), d_off.data_ptr(), n, width, stride, 2.0,
+                                          d_soff.data_ptr(), ns, d_seg.data_ptr(), d_seg_sta.data_ptr(), stream=st)
+            stream.synchronize()
+            assert np.array_equal(d_lab.cpu().numpy(), want[0]) and np.array_equal(d_sta.cpu().numpy(), want[2])
+            assert np.array_equal(bits(d_sc.cpu().numpy()), bits(want[1]))
+            assert np.array_equal(d_seg.cpu().numpy(), want_seg[0])
+            assert np.array_equal(d_seg_sta.cpu().numpy(), want_seg[1])
+        monkeypatch.delenv("LDGPU_SPAN_CHUNK_SPANS")
+        for chunk in (1, 3):
+            monkeypatch.setenv("LDGPU_TOPK_CHUNK_DOCS", str(chunk))
+            d_top = torch.full((n, 3), -7, dtype=torch.int32, device=dev)
+            d_top_s = torch.full((n, 3), -7.0, dtype=torch.float64, device=dev)
+            md.score_topk_utf8_device(d_data.data_ptr(), len(data), d_off.data_ptr(), n, 3, d_top.data_ptr(),
+                                      d_top_s.data_ptr(), stream=st)
+            stream.synchronize()
+            assert np.array_equal(d_top.cpu().numpy(), want_top[0])
+            assert np.array_equal(bits(d_top_s.cpu().numpy()), bits(want_top[1]))
+        monkeypatch.delenv("LDGPU_TOPK_CHUNK_DOCS")
 
 
 # ------------------------------------------------------------- device forms
