@@ -141,6 +141,10 @@ int ldgpu_model_info(const ldgpu_model* model, int32_t* mode, int64_t* n_keys,
 #define LDGPU_LAYOUT_TRIE               0x1000 /* count mode, labels-only calls on documents that are not
                                                   packed: every key (at most 4 bytes, one language each) in
                                                   an exact byte trie held in LDS; no filter, queue or verify */
+#define LDGPU_LAYOUT_TRIE_SUM           0x2000 /* set beside LDGPU_LAYOUT_TRIE: the trie's path-sum form --
+                                                  every root path names one language (at most 63 languages)
+                                                  and counts at most 4, so a node says what its whole path
+                                                  counts and a window position is counted once */
 int ldgpu_model_layout(const ldgpu_model* model, int32_t* flags);
 /* The model's language count (a caller sizing score buffers, e.g. the JNI
  * shim, takes it from the model rather than trusting its own). */

@@ -726,6 +726,7 @@ struct ldgpu_model {
     uint32_t* d_trie = nullptr;
     uint32_t trie_words = 0, trie_dead = 0;
     int trie_max_len = 0;
+    bool trie_sum = false;  // the image has the path-sum form
     int trie_wg_per_cu = 1;
     // the lists of the documents the trie kernel leaves: stream-ordered scratch
     // from a pool of the model's own that keeps its blocks across synchronises
@@ -1788,7 +1789,19 @@ int model_build(ldgpu_ctx* ctx, int32_t n_langs, const int32_t* gram_lengths, in
             tkeys.push_back(TrieKey{(uint32_t)keys[i], (uint8_t)len,
                                     (uint8_t)(((listed >> len) & 1u) ? lang : kTrieNoLang)});
         }
-        if (eligible) eligible = trie_build(tkeys, (kWgLds - per_wave) / 4u, trie);
+        // The path-sum form first (one image per model): the table must have
+        // it -- one language per root path, below kTrieSumMaxLangs, path sums
+        // of the lengths' multiplicities within kTrieSumMaxW -- else the form
+        // above.  Diagnostics: LDGPU_NO_TRIE_SUM=1.
+        bool sum = eligible && n_langs <= (int)kTrieSumMaxLangs;
+        if (const char* s = diag_env("LDGPU_NO_TRIE_SUM")) sum &= atoi(s) == 0;
+        if (sum) {
+            uint32_t mult[kTrieMaxLen + 1] = {};
+            for (int i = 0; i < n_grams; ++i)
+                if (gram_lengths[i] >= 1 && gram_lengths[i] <= kTrieMaxLen) ++mult[gram_lengths[i]];
+            sum = trie_build_sum(tkeys, mult, (kWgLds - per_wave) / 4u, trie);
+        }
+        if (eligible && !sum) eligible = trie_build(tkeys, (kWgLds - per_wave) / 4u, trie);
         if (eligible && trie.max_len < 1) eligible = false;  // (no counted key: nothing to walk)
         if (!eligible) trie.words.clear();
     }
@@ -1799,6 +1812,7 @@ int model_build(ldgpu_ctx* ctx, int32_t n_langs, const int32_t* gram_lengths, in
         m->trie_words = (uint32_t)trie.words.size();
         m->trie_dead = trie.dead;
         m->trie_max_len = trie.max_len;
+        m->trie_sum = trie.sum;
     }
     if (e == hipSuccess) e = upload(&m->d_slots, slots, &m->device_bytes);
     if (e == hipSuccess && nw > 0) e = upload(&m->d_wslots, wslots, &m->device_bytes);
@@ -1841,7 +1855,7 @@ int model_build(ldgpu_ctx* ctx, int32_t n_langs, const int32_t* gram_lengths, in
     if (m->d_trie && e == hipSuccess) {
         const size_t tl = trie_lds_bytes(m->trie_words, S, kScoreWaves, kBufWords);
         int r = 0;
-        e = trie_prepare(S, m->trie_max_len, tl, &r);
+        e = trie_prepare(S, m->trie_max_len, m->trie_sum, tl, &r);
         m->trie_wg_per_cu = std::max<int>(1, std::min<int>(r > 0 ? r : 1, (int)(163840 / tl)));
         // The default pool releases its blocks at every synchronise, so a host
         // pipeline that synchronises per chunk paid an allocation and a release
@@ -1865,9 +1879,9 @@ int model_build(ldgpu_ctx* ctx, int32_t n_langs, const int32_t* gram_lengths, in
     }
     if (diag_env("LDGPU_DEBUG"))
         fprintf(stderr, "[ldgpu] model: keys=%lld mode=%d direct=%u slices=%d bloom_words=%llu lds_bloom=%d lds=%zu B "
-                        "resident_api=%d wg_per_cu=%d pack=%d classes=%d trie_words=%u trie_wg_per_cu=%d\n",
+                        "resident_api=%d wg_per_cu=%d pack=%d classes=%d trie_words=%u trie_sum=%d trie_wg_per_cu=%d\n",
                 (long long)nk, m->mode, m->direct_words, S, (unsigned long long)bwords, (int)m->lds_filter, m->lds_bytes, resident,
-                m->wg_per_cu, (int)m->pack_ok, m->n_cls, m->trie_words, m->trie_wg_per_cu);
+                m->wg_per_cu, (int)m->pack_ok, m->n_cls, m->trie_words, (int)m->trie_sum, m->trie_wg_per_cu);
     if (e != hipSuccess) {
         model_free(m);
         return fail(e == hipErrorOutOfMemory ? LDGPU_ENOMEM : LDGPU_EDEVICE, "model upload: %s",
@@ -1913,6 +1927,7 @@ extern "C" int ldgpu_model_layout(const ldgpu_model* m, int32_t* flags) {
     if (b->d_wslots) f |= LDGPU_LAYOUT_WIDE_KEYS;
     if (b->d_nslots) f |= LDGPU_LAYOUT_NARROW_SLOTS;
     if (b->d_trie) f |= LDGPU_LAYOUT_TRIE;
+    if (b->d_trie && b->trie_sum) f |= LDGPU_LAYOUT_TRIE_SUM;
     if (b->direct_words) f |= LDGPU_LAYOUT_DIRECT;
     if (b->pack_ok) f |= LDGPU_LAYOUT_PACKS;
     if (b->n_cls && m->blocks.empty()) f |= LDGPU_LAYOUT_CLASSES;
@@ -2014,7 +2029,7 @@ int trie_launch(ldgpu_model* m, const ScoreParams& p, hipStream_t st) {
         int grid = (int)std::max<int64_t>(
             1, std::min<int64_t>((n + kScoreWaves - 1) / kScoreWaves, (int64_t)m->ctx->cus * m->trie_wg_per_cu));
         if (const char* g = diag_env("LDGPU_SCORE_GRID")) grid = std::max(1, atoi(g));
-        e = launch_trie(t, m->slices, m->trie_max_len, grid, st);
+        e = launch_trie(t, m->slices, m->trie_max_len, m->trie_sum, grid, st);
     }
     if (e == hipSuccess) {
         ScoreParams pi = p;

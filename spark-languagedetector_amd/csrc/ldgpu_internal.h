@@ -190,14 +190,16 @@ struct TrieParams {
     int32_t L;
     int32_t count_sign;         // sign of the table's one value
     int32_t maxg;               // max(G)
-    uint32_t mult[kTrieMaxLen + 1];  // multiplicity of n in G; 0: n is not listed or has no key
+    uint32_t mult[kTrieMaxLen + 1];  // multiplicity of n in G; 0: n is not listed or has no key (the
+                                     // path-sum form does not read it: its image holds the weights)
     int64_t* left;              // out: the documents left to score_kernel ([n_docs])
     unsigned long long* n_left; // out: their count (zeroed by the caller)
 };
-// slices = ceil(L / 64), max_len = the longest counted key (1..kTrieMaxLen)
-hipError_t launch_trie(const TrieParams& p, int slices, int max_len, int grid, hipStream_t stream);
+// slices = ceil(L / 64), max_len = the longest counted key (1..kTrieMaxLen),
+// sum: the image has the path-sum form (TrieImage::sum; slices == 1)
+hipError_t launch_trie(const TrieParams& p, int slices, int max_len, bool sum, int grid, hipStream_t stream);
 // sets the dynamic-LDS limit and returns the resident workgroups per CU
-hipError_t trie_prepare(int slices, int max_len, size_t lds_bytes, int* blocks_per_cu);
+hipError_t trie_prepare(int slices, int max_len, bool sum, size_t lds_bytes, int* blocks_per_cu);
 
 // General-key scoring (ldgpu_general.hip): models with a gram length beyond
 // kMaxWideGram -- keys of any length in one table (GenSlot), compared byte for

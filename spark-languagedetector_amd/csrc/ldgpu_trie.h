@@ -24,6 +24,24 @@
 //
 // A walk reads slots up to base + 255 for any text byte, so every base leaves
 // 256 slots to the end of the image.
+//
+// The PATH-SUM form (trie_build_sum) keeps the packing -- rows, bases, the dead
+// base and the empty slots' check bytes are those of the form above -- and
+// changes what an entry says:
+//
+//   entry = child base | check byte << 16 | payload << 24
+//
+//   payload    0: no counted key on the path from the root to this node (the
+//              node included).  Otherwise 1 + language + 64 (W - 1): the one
+//              language of the path's counted keys, and W = the sum of
+//              mult[length] over them.  W grows along a path, so the payload
+//              does, and the deepest node a walk reaches says all the walk
+//              counts: `payload & 63` is the counter index (language + 1),
+//              `(payload >> 6) + 1` the increment.  Whole entries compare by
+//              payload first.
+//
+// A table has this form when every root path names at most one language, every
+// language is below kTrieSumMaxLangs and every W is at most kTrieSumMaxW.
 #pragma once
 
 #include <algorithm>
@@ -36,6 +54,8 @@ constexpr int kTrieMaxLen = 4;
 constexpr uint32_t kTrieNoLang = 0xffu;
 constexpr uint32_t kTrieMaxLangs = 254;      // languages 0..253: the counter index is the entry's byte
 constexpr uint32_t kTrieMaxSlots = 16384;    // 64 KiB: a byte offset fits the entry's 16 bits
+constexpr uint32_t kTrieSumMaxLangs = 63;    // path-sum form: languages 0..62 (counter index language + 1 <= 63)
+constexpr uint32_t kTrieSumMaxW = 4;         // path-sum form: the largest sum of multiplicities on a path
 
 struct TrieKey {
     uint32_t bytes;  // the key's bytes little-endian (byte 0 first), zero above len
@@ -49,6 +69,7 @@ struct TrieImage {
     uint32_t nodes = 0;           // trie nodes below the root
     uint32_t rows = 0;            // nodes with children (the root included)
     int max_len = 0;              // the longest counted key
+    bool sum = false;             // the path-sum form (trie_build_sum)
 };
 
 constexpr uint32_t trie_entry(uint32_t check, uint32_t lang, uint32_t base_slot) {
@@ -66,14 +87,32 @@ inline uint32_t trie_step(const TrieImage& t, uint32_t e, uint8_t c) {
     return trie_check(n) == c ? n : t.dead;
 }
 
-// Builds the image of `keys` (distinct) within max_slots slots.  False: a key
-// out of the rule, two languages for one key, or no packing within max_slots.
-inline bool trie_build(const std::vector<TrieKey>& keys, uint32_t max_slots, TrieImage& out) {
+// the path-sum form's entry and its parts
+constexpr uint32_t trie_sum_payload_of(uint32_t lang, uint32_t w) { return 1u + lang + 64u * (w - 1u); }
+constexpr uint32_t trie_sum_entry(uint32_t check, uint32_t payload, uint32_t base_slot) {
+    return base_slot * 4u | check << 16 | payload << 24;
+}
+constexpr uint32_t trie_sum_check(uint32_t e) { return (e >> 16) & 0xffu; }
+constexpr uint32_t trie_sum_payload(uint32_t e) { return e >> 24; }
+constexpr uint32_t trie_sum_base_slot(uint32_t e) { return (e & 0xffffu) >> 2; }
+constexpr uint32_t trie_sum_counter(uint32_t payload) { return payload & 63u; }   // language + 1
+constexpr uint32_t trie_sum_weight(uint32_t payload) { return (payload >> 6) + 1u; }
+inline uint32_t trie_sum_step(const TrieImage& t, uint32_t e, uint8_t c) {
+    const uint32_t n = t.words[trie_sum_base_slot(e) + c];
+    return trie_sum_check(n) == c ? n : t.dead;
+}
+
+// Both forms' builder.  mult == nullptr: the form of trie_build.  Otherwise the
+// path-sum form with mult[1..kTrieMaxLen], the multiplicity of each key length
+// (a key whose length has multiplicity 0 is not counted, as one of kTrieNoLang).
+inline bool trie_build_form(const std::vector<TrieKey>& keys, uint32_t max_slots, const uint32_t* mult,
+                            TrieImage& out) {
     struct Node {
         uint32_t parent;
         uint8_t byte, lang;
         std::vector<uint32_t> kids;  // node indices
         uint32_t base = 0;           // slot index of the row (nodes with kids)
+        uint32_t payload = 0;        // path-sum form
     };
     max_slots = std::min(max_slots, kTrieMaxSlots);
     if (max_slots < 512) return false;
@@ -83,8 +122,8 @@ inline bool trie_build(const std::vector<TrieKey>& keys, uint32_t max_slots, Tri
     std::vector<TrieKey> ks;
     for (const TrieKey& k : keys) {
         if (k.len < 1 || k.len > kTrieMaxLen) return false;
-        if (k.lang == kTrieNoLang) continue;
-        if (k.lang >= kTrieMaxLangs) return false;
+        if (k.lang == kTrieNoLang || (mult && !mult[k.len])) continue;
+        if (k.lang >= (mult ? kTrieSumMaxLangs : kTrieMaxLangs)) return false;
         ks.push_back(k);
     }
     // (every key is a node of its own and every node takes a slot: more counted
@@ -110,6 +149,28 @@ inline bool trie_build(const std::vector<TrieKey>& keys, uint32_t max_slots, Tri
         out.max_len = std::max(out.max_len, (int)k.len);
     }
     out.nodes = (uint32_t)nodes.size() - 1;
+    out.sum = mult != nullptr;
+    if (mult) {
+        // (a node's index is above its parent's: one pass in index order)
+        std::vector<uint8_t> depth(nodes.size(), 0), plang(nodes.size(), (uint8_t)kTrieNoLang);
+        std::vector<uint32_t> w(nodes.size(), 0);
+        for (uint32_t i = 1; i < nodes.size(); ++i) {
+            const uint32_t up = nodes[i].parent;
+            depth[i] = (uint8_t)(depth[up] + 1);
+            plang[i] = plang[up];
+            w[i] = w[up];
+            if (nodes[i].lang != kTrieNoLang) {
+                if (plang[i] != kTrieNoLang && plang[i] != nodes[i].lang) return false;  // two languages on a path
+                plang[i] = nodes[i].lang;
+                w[i] += mult[depth[i]];
+            }
+            if (w[i] > kTrieSumMaxW) return false;
+            nodes[i].payload = w[i] ? trie_sum_payload_of(plang[i], w[i]) : 0u;
+        }
+    }
+    const auto entry = [&](uint32_t check, uint32_t lang, uint32_t payload, uint32_t base_slot) {
+        return mult ? trie_sum_entry(check, payload, base_slot) : trie_entry(check, lang, base_slot);
+    };
 
     // first-fit row displacement, largest rows first; the root's row is slots
     // 0..255, exclusive.  A row may start below slot 256 (its base only has to
@@ -162,12 +223,12 @@ inline bool trie_build(const std::vector<TrieKey>& keys, uint32_t max_slots, Tri
         if (used_base[b]) top = b;
     const uint32_t n_slots = (top + 256 + 3) & ~3u;
     if (n_slots > max_slots) return false;
-    out.dead = trie_entry(0, kTrieNoLang, dead_base);
+    out.dead = entry(0, kTrieNoLang, 0, dead_base);
     out.words.assign(n_slots, 0u);
     for (uint32_t s = 0; s < n_slots; ++s) {
         if (owner[s] >= 0) {
             const Node& n = nodes[(size_t)owner[s]];
-            out.words[s] = trie_entry(n.byte, n.lang, n.kids.empty() ? dead_base : n.base);
+            out.words[s] = entry(n.byte, n.lang, n.payload, n.kids.empty() ? dead_base : n.base);
             continue;
         }
         // an empty slot: a check byte that names no row
@@ -175,9 +236,23 @@ inline bool trie_build(const std::vector<TrieKey>& keys, uint32_t max_slots, Tri
         for (int t = 0; t < 256 && c < 0; ++t)
             if ((uint32_t)t > s || !used_base[s - (uint32_t)t]) c = t;
         if (c < 0) return false;
-        out.words[s] = trie_entry((uint32_t)c, kTrieNoLang, dead_base);
+        out.words[s] = entry((uint32_t)c, kTrieNoLang, 0, dead_base);
     }
     return true;
+}
+
+// Builds the image of `keys` (distinct) within max_slots slots.  False: a key
+// out of the rule, two languages for one key, or no packing within max_slots.
+inline bool trie_build(const std::vector<TrieKey>& keys, uint32_t max_slots, TrieImage& out) {
+    return trie_build_form(keys, max_slots, nullptr, out);
+}
+
+// The path-sum form of the same keys: mult[1..kTrieMaxLen] (mult[0] unused).
+// False also for a table that has not this form: two languages on one root
+// path, a language of kTrieSumMaxLangs or above, a W above kTrieSumMaxW.
+inline bool trie_build_sum(const std::vector<TrieKey>& keys, const uint32_t (&mult)[kTrieMaxLen + 1],
+                           uint32_t max_slots, TrieImage& out) {
+    return trie_build_form(keys, max_slots, mult, out);
 }
 
 // bytes of LDS the trie kernel needs per workgroup of `waves` waves: the image,

@@ -30,6 +30,9 @@
 //              the document's end unchecked (the bytes there are the next
 //              document's, or the buffer's padding)
 //   label      the count argmax (first maximum), as score_kernel's
+// A table in the path-sum form (ldgpu_trie.h: one language and a count of at
+// most 4 per root path; trie_kernel<1, maxlen, true>) is counted once per window
+// position instead of once per (position, depth): trie_doc_sum below.
 // Every other document -- shorter than maxg (partial windows), longer than 256
 // bytes, or in a group the staging buffer does not hold -- gets label -1 and
 // is appended to a list (p.left, its length counted in *p.n_left); an indirect
@@ -71,16 +74,18 @@ __device__ __forceinline__ void group_dma(const TrieParams& p, int64_t s0, uint3
 
 // the label of the document counted in cnt (first maximum of the counts: the
 // fold of c adds of the table's one value is strictly monotone in c); clears
-// the counters -- score_kernel's count_argmax
-template <int S>
+// the counters -- score_kernel's count_argmax.  Language l's counter is
+// cnt[l + OFS] (the path-sum form counts at the payload's index, language + 1).
+template <int S, int OFS = 0>
 __device__ __forceinline__ int count_argmax(const TrieParams& p, uint32_t* cnt, int lane) {
+    static_assert(OFS == 0 || S == 1, "the shifted counters are one slice");
     uint32_t best = 0;
 #pragma unroll
     for (int s = 0; s < S; ++s) {
         const int l = 64 * s + lane;
         if (l < p.L) {
-            const uint32_t c = cnt[l];
-            cnt[l] = 0;
+            const uint32_t c = cnt[l + OFS];
+            cnt[l + OFS] = 0;
             const uint32_t k = p.count_sign > 0 ? c : (p.count_sign < 0 ? 0xffffffu - c : 0u);
             best = max(best, (k << 8) | (uint32_t)(255 - l));
         }
@@ -127,8 +132,56 @@ __device__ __forceinline__ void count_depth(const TrieParams& p, uint32_t* cnt, 
     }
 }
 
+// The path-sum form (ldgpu_trie.h), from the run bytes on: every node's payload
+// says what the whole path to it counts, so a walk is counted once, at the
+// deepest node it reaches inside the document.
+//   step d -> d + 1   live = check == text byte && the window of d + 1 bytes
+//              ends inside the document (cut.in[k + d], and-ed into the
+//              compare's lane mask); a walk that is not live goes dead
+//   slot k     m = the maximum over the slot's entries of all depths (whole
+//              entries order by payload, and the payload grows along a path);
+//              payload(m) != 0 and position 4 lane + k inside the document
+//              (cut.in[k]: the depth-1 read is unchecked): one LDS add of the
+//              payload's weight at the payload's counter (language + 1 <= 63)
+// p.mult is not read: the weights are in the image.
+template <int MAXD>
+__device__ __forceinline__ int trie_doc_sum(const TrieParams& p, uint32_t dead, uint32_t* cnt, const uint32_t (&b)[7],
+                                            const uint32_t (&off)[7], int lane, const TailCut& cut) {
+    uint32_t e[4], m[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) m[k] = e[k] = lds_word(off[k]);  // (the direct table at LDS address 0: no check)
+    bool live[4] = {true, true, true, true};
+#pragma unroll
+    for (int d = 1; d < MAXD; ++d) {
+        // The step to depth 4 only in the lanes where a walk is still live (about
+        // one in eight on text): the other lanes' reads of the dead row took part
+        // in the banking for nothing.  The test is three s_or_b64 of the previous
+        // step's lane masks.  One branch for the four reads, never one per slot.
+        if (d == 3 && !(live[0] | live[1] | live[2] | live[3])) continue;
+        uint32_t n[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) n[k] = lds_word((e[k] & 0xffffu) + off[k + d]);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const bool in = __builtin_amdgcn_inverse_ballot_w64(cut.in[k + d]);
+            live[k] = __builtin_amdgcn_ubfe(n[k], 16, 8) == b[k + d] && in;
+            e[k] = live[k] ? n[k] : dead;
+            m[k] = max(m[k], e[k]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t pay = m[k] >> 24;
+        const bool in = __builtin_amdgcn_inverse_ballot_w64(cut.in[k]);
+        if (pay != 0 && in)
+            __hip_atomic_fetch_add(&cnt[pay & 63u], (pay >> 6) + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    return count_argmax<1, 1>(p, cnt, lane);
+}
+
 // One staged document of maxg..256 bytes at byte `base` of the wave's buffer.
-template <int S, int MAXD>
+// SUM: the image has the path-sum form.
+template <int S, int MAXD, bool SUM>
 __device__ __forceinline__ int trie_doc(const TrieParams& p, uint32_t dead, uint32_t* cnt,
                                         const uint32_t* buf, uint32_t base, int32_t len, int lane, TailCut& cut) {
     // run bytes 0..6 of the lane's four positions.  Bound: lane 63 reads dwords
@@ -145,6 +198,7 @@ __device__ __forceinline__ int trie_doc(const TrieParams& p, uint32_t dead, uint
         off[j] = b[j] << 2;
     }
     tail_cut<MAXD>(cut, len, lane);
+    if constexpr (SUM) return trie_doc_sum<MAXD>(p, dead, cnt, b, off, lane, cut);
     uint32_t e[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) e[k] = lds_word(off[k]);  // (the direct table at LDS address 0: no check)
@@ -171,8 +225,9 @@ __device__ __forceinline__ int trie_doc(const TrieParams& p, uint32_t dead, uint
     return count_argmax<S>(p, cnt, lane);
 }
 
-template <int S, int MAXD>
+template <int S, int MAXD, bool SUM>
 __global__ __launch_bounds__(kScoreWaves * 64, kScoreMinWgPerCu * kScoreWaves / 4) void trie_kernel(const TrieParams p) {
+    static_assert(!SUM || S == 1, "the path-sum form has one counter slice");
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -248,7 +303,7 @@ __global__ __launch_bounds__(kScoreWaves * 64, kScoreMinWgPerCu * kScoreWaves / 
             const uint32_t base = blo - (uint32_t)s0;
             int lab;
             if (staged && len >= p.maxg && len <= 256) {
-                lab = trie_doc<S, MAXD>(p, dead, cnt, cur, base, len, lane, cut);
+                lab = trie_doc<S, MAXD, SUM>(p, dead, cnt, cur, base, len, lane, cut);
             } else {
                 // left to the indirect launch of score_kernel
                 lab = 0xff;
@@ -266,44 +321,45 @@ __global__ __launch_bounds__(kScoreWaves * 64, kScoreMinWgPerCu * kScoreWaves / 
     if (lane < prev_cnt) p.labels[prev_g0 + lane] = label_of(labels[lane]);
 }
 
-template <int S, int MAXD>
+template <int S, int MAXD, bool SUM>
 hipError_t launch_k(const TrieParams& p, int grid, size_t lds, hipStream_t stream) {
-    hipLaunchKernelGGL((trie_kernel<S, MAXD>), dim3(grid), dim3(kScoreWaves * 64), lds, stream, p);
+    hipLaunchKernelGGL((trie_kernel<S, MAXD, SUM>), dim3(grid), dim3(kScoreWaves * 64), lds, stream, p);
     return hipGetLastError();
 }
-template <int S>
+template <int S, bool SUM = false>
 hipError_t launch_s(const TrieParams& p, int max_len, int grid, size_t lds, hipStream_t stream) {
     switch (max_len) {
-        case 1: return launch_k<S, 1>(p, grid, lds, stream);
-        case 2: return launch_k<S, 2>(p, grid, lds, stream);
-        case 3: return launch_k<S, 3>(p, grid, lds, stream);
-        case 4: return launch_k<S, 4>(p, grid, lds, stream);
+        case 1: return launch_k<S, 1, SUM>(p, grid, lds, stream);
+        case 2: return launch_k<S, 2, SUM>(p, grid, lds, stream);
+        case 3: return launch_k<S, 3, SUM>(p, grid, lds, stream);
+        case 4: return launch_k<S, 4, SUM>(p, grid, lds, stream);
         default: return hipErrorInvalidValue;
     }
 }
 
-template <int S, int MAXD>
+template <int S, int MAXD, bool SUM>
 hipError_t prepare_k(size_t lds, int* blocks) {
-    const void* f = reinterpret_cast<const void*>(&trie_kernel<S, MAXD>);
+    const void* f = reinterpret_cast<const void*>(&trie_kernel<S, MAXD, SUM>);
     hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, f, kScoreWaves * 64, lds);
 }
-template <int S>
+template <int S, bool SUM = false>
 hipError_t prepare_s(int max_len, size_t lds, int* blocks) {
     switch (max_len) {
-        case 1: return prepare_k<S, 1>(lds, blocks);
-        case 2: return prepare_k<S, 2>(lds, blocks);
-        case 3: return prepare_k<S, 3>(lds, blocks);
-        case 4: return prepare_k<S, 4>(lds, blocks);
+        case 1: return prepare_k<S, 1, SUM>(lds, blocks);
+        case 2: return prepare_k<S, 2, SUM>(lds, blocks);
+        case 3: return prepare_k<S, 3, SUM>(lds, blocks);
+        case 4: return prepare_k<S, 4, SUM>(lds, blocks);
         default: return hipErrorInvalidValue;
     }
 }
 
 }  // namespace
 
-hipError_t launch_trie(const TrieParams& p, int slices, int max_len, int grid, hipStream_t stream) {
+hipError_t launch_trie(const TrieParams& p, int slices, int max_len, bool sum, int grid, hipStream_t stream) {
     const size_t lds = trie_lds_bytes(p.image_words, slices, kScoreWaves, kBufWords);
+    if (sum) return slices == 1 ? launch_s<1, true>(p, max_len, grid, lds, stream) : hipErrorInvalidValue;
     switch (slices) {
         case 1: return launch_s<1>(p, max_len, grid, lds, stream);
         case 2: return launch_s<2>(p, max_len, grid, lds, stream);
@@ -313,7 +369,8 @@ hipError_t launch_trie(const TrieParams& p, int slices, int max_len, int grid, h
     }
 }
 
-hipError_t trie_prepare(int slices, int max_len, size_t lds_bytes, int* blocks_per_cu) {
+hipError_t trie_prepare(int slices, int max_len, bool sum, size_t lds_bytes, int* blocks_per_cu) {
+    if (sum) return slices == 1 ? prepare_s<1, true>(max_len, lds_bytes, blocks_per_cu) : hipErrorInvalidValue;
     switch (slices) {
         case 1: return prepare_s<1>(max_len, lds_bytes, blocks_per_cu);
         case 2: return prepare_s<2>(max_len, lds_bytes, blocks_per_cu);
