@@ -26,6 +26,8 @@ with LDGPU_NO_TRIE=1 keep the LDS-Bloom path of these tables covered.
   languages  70, 134, 200 and 254 languages (2, 3, 4 counter slices), the
              winners at or above 64, 128 and 192
   scores     the same model asked for scores or top-k gives unchanged results
+             (device-pointer, UTF-8 and chunked calls, and a negative table
+             value: test_gpu_trie_calls.py)
 
 Hand mutations of ldgpu_trie.hip, each built once and not committed (the check
 compare dropped; the tail condition dropped for depth 4): see DESIGN.md for the
