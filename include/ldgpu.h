@@ -145,6 +145,10 @@ int ldgpu_model_info(const ldgpu_model* model, int32_t* mode, int64_t* n_keys,
                                                   every root path names one language (at most 63 languages)
                                                   and counts at most 4, so a node says what its whole path
                                                   counts and a window position is counted once */
+#define LDGPU_LAYOUT_TRIE_PAIR          0x4000 /* set beside LDGPU_LAYOUT_TRIE and _TRIE_SUM: the path-sum
+                                                  form with one counter per (language, count W) pair, a
+                                                  node holding its counter's offset (largest W times the
+                                                  language count at most 63) */
 int ldgpu_model_layout(const ldgpu_model* model, int32_t* flags);
 /* The model's language count (a caller sizing score buffers, e.g. the JNI
  * shim, takes it from the model rather than trusting its own). */

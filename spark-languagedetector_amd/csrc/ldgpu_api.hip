@@ -727,6 +727,8 @@ struct ldgpu_model {
     uint32_t trie_words = 0, trie_dead = 0;
     int trie_max_len = 0;
     bool trie_sum = false;  // the image has the path-sum form
+    bool trie_pair = false; // ... with the pair payload (one counter per (language, W))
+    uint32_t trie_wmax = 0; // path-sum form: the largest W in the image
     int trie_wg_per_cu = 1;
     // the lists of the documents the trie kernel leaves: stream-ordered scratch
     // from a pool of the model's own that keeps its blocks across synchronises
@@ -1799,7 +1801,15 @@ int model_build(ldgpu_ctx* ctx, int32_t n_langs, const int32_t* gram_lengths, in
             uint32_t mult[kTrieMaxLen + 1] = {};
             for (int i = 0; i < n_grams; ++i)
                 if (gram_lengths[i] >= 1 && gram_lengths[i] <= kTrieMaxLen) ++mult[gram_lengths[i]];
-            sum = trie_build_sum(tkeys, mult, (kWgLds - per_wave) / 4u, trie);
+            // Its pair form first, where every (language, W) has a counter
+            // among the wave's 64: Wmax * L <= 63.  It is the path-sum form
+            // with that one bound more, which the builder tests before it
+            // packs a row, so a model's trie is still built once.
+            // Diagnostics: LDGPU_NO_TRIE_PAIR=1.
+            bool pair = true;
+            if (const char* s = diag_env("LDGPU_NO_TRIE_PAIR")) pair = atoi(s) == 0;
+            if (!pair || !trie_build_pair(tkeys, mult, (uint32_t)n_langs, (kWgLds - per_wave) / 4u, trie))
+                sum = trie_build_sum(tkeys, mult, (kWgLds - per_wave) / 4u, trie);
         }
         if (eligible && !sum) eligible = trie_build(tkeys, (kWgLds - per_wave) / 4u, trie);
         if (eligible && trie.max_len < 1) eligible = false;  // (no counted key: nothing to walk)
@@ -1813,6 +1823,8 @@ int model_build(ldgpu_ctx* ctx, int32_t n_langs, const int32_t* gram_lengths, in
         m->trie_dead = trie.dead;
         m->trie_max_len = trie.max_len;
         m->trie_sum = trie.sum;
+        m->trie_pair = trie.pair;
+        m->trie_wmax = trie.wmax;
     }
     if (e == hipSuccess) e = upload(&m->d_slots, slots, &m->device_bytes);
     if (e == hipSuccess && nw > 0) e = upload(&m->d_wslots, wslots, &m->device_bytes);
@@ -1855,7 +1867,7 @@ int model_build(ldgpu_ctx* ctx, int32_t n_langs, const int32_t* gram_lengths, in
     if (m->d_trie && e == hipSuccess) {
         const size_t tl = trie_lds_bytes(m->trie_words, S, kScoreWaves, kBufWords);
         int r = 0;
-        e = trie_prepare(S, m->trie_max_len, m->trie_sum, tl, &r);
+        e = trie_prepare(S, m->trie_max_len, m->trie_sum, m->trie_pair, tl, &r);
         m->trie_wg_per_cu = std::max<int>(1, std::min<int>(r > 0 ? r : 1, (int)(163840 / tl)));
         // The default pool releases its blocks at every synchronise, so a host
         // pipeline that synchronises per chunk paid an allocation and a release
@@ -1879,9 +1891,10 @@ int model_build(ldgpu_ctx* ctx, int32_t n_langs, const int32_t* gram_lengths, in
     }
     if (diag_env("LDGPU_DEBUG"))
         fprintf(stderr, "[ldgpu] model: keys=%lld mode=%d direct=%u slices=%d bloom_words=%llu lds_bloom=%d lds=%zu B "
-                        "resident_api=%d wg_per_cu=%d pack=%d classes=%d trie_words=%u trie_sum=%d trie_wg_per_cu=%d\n",
+                        "resident_api=%d wg_per_cu=%d pack=%d classes=%d trie_words=%u trie_sum=%d trie_pair=%d trie_wmax=%u trie_wg_per_cu=%d\n",
                 (long long)nk, m->mode, m->direct_words, S, (unsigned long long)bwords, (int)m->lds_filter, m->lds_bytes, resident,
-                m->wg_per_cu, (int)m->pack_ok, m->n_cls, m->trie_words, (int)m->trie_sum, m->trie_wg_per_cu);
+                m->wg_per_cu, (int)m->pack_ok, m->n_cls, m->trie_words, (int)m->trie_sum, (int)m->trie_pair, m->trie_wmax,
+                m->trie_wg_per_cu);
     if (e != hipSuccess) {
         model_free(m);
         return fail(e == hipErrorOutOfMemory ? LDGPU_ENOMEM : LDGPU_EDEVICE, "model upload: %s",
@@ -1928,6 +1941,7 @@ extern "C" int ldgpu_model_layout(const ldgpu_model* m, int32_t* flags) {
     if (b->d_nslots) f |= LDGPU_LAYOUT_NARROW_SLOTS;
     if (b->d_trie) f |= LDGPU_LAYOUT_TRIE;
     if (b->d_trie && b->trie_sum) f |= LDGPU_LAYOUT_TRIE_SUM;
+    if (b->d_trie && b->trie_pair) f |= LDGPU_LAYOUT_TRIE_PAIR;
     if (b->direct_words) f |= LDGPU_LAYOUT_DIRECT;
     if (b->pack_ok) f |= LDGPU_LAYOUT_PACKS;
     if (b->n_cls && m->blocks.empty()) f |= LDGPU_LAYOUT_CLASSES;
@@ -2020,6 +2034,7 @@ int trie_launch(ldgpu_model* m, const ScoreParams& p, hipStream_t st) {
         t.image = m->d_trie;
         t.image_words = m->trie_words;
         t.dead = m->trie_dead;
+        t.wmax = m->trie_wmax;
         t.L = m->L;
         t.count_sign = m->count_sign;
         t.maxg = p.maxg;
@@ -2029,7 +2044,7 @@ int trie_launch(ldgpu_model* m, const ScoreParams& p, hipStream_t st) {
         int grid = (int)std::max<int64_t>(
             1, std::min<int64_t>((n + kScoreWaves - 1) / kScoreWaves, (int64_t)m->ctx->cus * m->trie_wg_per_cu));
         if (const char* g = diag_env("LDGPU_SCORE_GRID")) grid = std::max(1, atoi(g));
-        e = launch_trie(t, m->slices, m->trie_max_len, m->trie_sum, grid, st);
+        e = launch_trie(t, m->slices, m->trie_max_len, m->trie_sum, m->trie_pair, grid, st);
     }
     if (e == hipSuccess) {
         ScoreParams pi = p;

@@ -187,6 +187,7 @@ struct TrieParams {
     const uint32_t* image;      // the trie image (TrieImage::words)
     uint32_t image_words;       // a multiple of 4
     uint32_t dead;              // the dead entry
+    uint32_t wmax;              // the pair form: the largest W in the image (wmax * L <= 63)
     int32_t L;
     int32_t count_sign;         // sign of the table's one value
     int32_t maxg;               // max(G)
@@ -196,10 +197,12 @@ struct TrieParams {
     unsigned long long* n_left; // out: their count (zeroed by the caller)
 };
 // slices = ceil(L / 64), max_len = the longest counted key (1..kTrieMaxLen),
-// sum: the image has the path-sum form (TrieImage::sum; slices == 1)
-hipError_t launch_trie(const TrieParams& p, int slices, int max_len, bool sum, int grid, hipStream_t stream);
+// sum: the image has the path-sum form (TrieImage::sum; slices == 1), pair:
+// with the pair payload (TrieImage::pair; p.wmax set)
+hipError_t launch_trie(const TrieParams& p, int slices, int max_len, bool sum, bool pair, int grid,
+                       hipStream_t stream);
 // sets the dynamic-LDS limit and returns the resident workgroups per CU
-hipError_t trie_prepare(int slices, int max_len, bool sum, size_t lds_bytes, int* blocks_per_cu);
+hipError_t trie_prepare(int slices, int max_len, bool sum, bool pair, size_t lds_bytes, int* blocks_per_cu);
 
 // General-key scoring (ldgpu_general.hip): models with a gram length beyond
 // kMaxWideGram -- keys of any length in one table (GenSlot), compared byte for

@@ -42,6 +42,20 @@
 //
 // A table has this form when every root path names at most one language, every
 // language is below kTrieSumMaxLangs and every W is at most kTrieSumMaxW.
+//
+// The PAIR form (trie_build_pair) is the path-sum form with another payload:
+// every pair (language l, W) has a counter of its own, and the payload is that
+// counter's BYTE offset in the wave's counter area as it stands:
+//
+//   payload    0: nothing counted.  Otherwise 4 * slot, slot = 1 + l + L (W - 1),
+//              L the model's language count.  Along a path the language is
+//              fixed and W grows, so the payload still grows and whole entries
+//              still compare by it.  A walk adds 1 at its payload's offset; the
+//              label's count of language l is the sum of w * counter[1 + l +
+//              L (w - 1)] over w = 1..Wmax.
+//
+// A table has this form when it has the path-sum form and Wmax * L <= 63, Wmax
+// the largest W in the image (TrieImage::wmax): the counter area stays 64 words.
 #pragma once
 
 #include <algorithm>
@@ -56,6 +70,7 @@ constexpr uint32_t kTrieMaxLangs = 254;      // languages 0..253: the counter in
 constexpr uint32_t kTrieMaxSlots = 16384;    // 64 KiB: a byte offset fits the entry's 16 bits
 constexpr uint32_t kTrieSumMaxLangs = 63;    // path-sum form: languages 0..62 (counter index language + 1 <= 63)
 constexpr uint32_t kTrieSumMaxW = 4;         // path-sum form: the largest sum of multiplicities on a path
+constexpr uint32_t kTriePairMaxSlot = 63;    // pair form: counters 1..63, Wmax * L <= 63 (slot 0: nothing counted)
 
 struct TrieKey {
     uint32_t bytes;  // the key's bytes little-endian (byte 0 first), zero above len
@@ -69,7 +84,9 @@ struct TrieImage {
     uint32_t nodes = 0;           // trie nodes below the root
     uint32_t rows = 0;            // nodes with children (the root included)
     int max_len = 0;              // the longest counted key
-    bool sum = false;             // the path-sum form (trie_build_sum)
+    bool sum = false;             // the path-sum form (trie_build_sum, trie_build_pair)
+    bool pair = false;            // ... with the pair payload (trie_build_pair)
+    uint32_t wmax = 0;            // path-sum form: the largest W in the image
 };
 
 constexpr uint32_t trie_entry(uint32_t check, uint32_t lang, uint32_t base_slot) {
@@ -102,11 +119,25 @@ inline uint32_t trie_sum_step(const TrieImage& t, uint32_t e, uint8_t c) {
     return trie_sum_check(n) == c ? n : t.dead;
 }
 
-// Both forms' builder.  mult == nullptr: the form of trie_build.  Otherwise the
+// the pair form's payload and its parts (n_langs: the model's language count)
+constexpr uint32_t trie_pair_slot_of(uint32_t lang, uint32_t w, uint32_t n_langs) {
+    return 1u + lang + n_langs * (w - 1u);
+}
+constexpr uint32_t trie_pair_payload_of(uint32_t lang, uint32_t w, uint32_t n_langs) {
+    return 4u * trie_pair_slot_of(lang, w, n_langs);
+}
+constexpr uint32_t trie_pair_slot(uint32_t payload) { return payload >> 2; }  // payload != 0
+constexpr uint32_t trie_pair_lang(uint32_t payload, uint32_t n_langs) { return (trie_pair_slot(payload) - 1u) % n_langs; }
+constexpr uint32_t trie_pair_weight(uint32_t payload, uint32_t n_langs) {
+    return (trie_pair_slot(payload) - 1u) / n_langs + 1u;
+}
+
+// All forms' builder.  mult == nullptr: the form of trie_build.  Otherwise the
 // path-sum form with mult[1..kTrieMaxLen], the multiplicity of each key length
-// (a key whose length has multiplicity 0 is not counted, as one of kTrieNoLang).
+// (a key whose length has multiplicity 0 is not counted, as one of kTrieNoLang);
+// pair_langs != 0: the pair payload for a model of pair_langs languages.
 inline bool trie_build_form(const std::vector<TrieKey>& keys, uint32_t max_slots, const uint32_t* mult,
-                            TrieImage& out) {
+                            TrieImage& out, uint32_t pair_langs = 0) {
     struct Node {
         uint32_t parent;
         uint8_t byte, lang;
@@ -150,6 +181,7 @@ inline bool trie_build_form(const std::vector<TrieKey>& keys, uint32_t max_slots
     }
     out.nodes = (uint32_t)nodes.size() - 1;
     out.sum = mult != nullptr;
+    out.pair = mult != nullptr && pair_langs != 0;
     if (mult) {
         // (a node's index is above its parent's: one pass in index order)
         std::vector<uint8_t> depth(nodes.size(), 0), plang(nodes.size(), (uint8_t)kTrieNoLang);
@@ -165,7 +197,17 @@ inline bool trie_build_form(const std::vector<TrieKey>& keys, uint32_t max_slots
                 w[i] += mult[depth[i]];
             }
             if (w[i] > kTrieSumMaxW) return false;
+            out.wmax = std::max(out.wmax, w[i]);
             nodes[i].payload = w[i] ? trie_sum_payload_of(plang[i], w[i]) : 0u;
+        }
+        if (pair_langs) {
+            // every language below pair_langs, and the last counter within the area
+            if (out.wmax * pair_langs > kTriePairMaxSlot) return false;
+            for (uint32_t i = 1; i < nodes.size(); ++i) {
+                if (!w[i]) continue;
+                if (plang[i] >= pair_langs) return false;
+                nodes[i].payload = trie_pair_payload_of(plang[i], w[i], pair_langs);
+            }
         }
     }
     const auto entry = [&](uint32_t check, uint32_t lang, uint32_t payload, uint32_t base_slot) {
@@ -255,9 +297,20 @@ inline bool trie_build_sum(const std::vector<TrieKey>& keys, const uint32_t (&mu
     return trie_build_form(keys, max_slots, mult, out);
 }
 
+// The pair form of the same keys for a model of n_langs languages.  False also
+// for a table that has the path-sum form but not this one: Wmax * n_langs above
+// kTriePairMaxSlot, or a counted language of n_langs or above.
+inline bool trie_build_pair(const std::vector<TrieKey>& keys, const uint32_t (&mult)[kTrieMaxLen + 1],
+                            uint32_t n_langs, uint32_t max_slots, TrieImage& out) {
+    return n_langs >= 1 && trie_build_form(keys, max_slots, mult, out, n_langs);
+}
+
 // bytes of LDS the trie kernel needs per workgroup of `waves` waves: the image,
-// then per wave the language counters, the double-buffered staging and the
-// group's labels (one byte each: a language below kTrieMaxLangs, or 0xff = -1)
+// then per wave the language counters, the double-buffered staging and 64
+// spare bytes.  The kernel staged a group's labels there until they moved into
+// a register; nothing reads or writes them now.  They stay in the sum so that
+// the footprint and the builder's slot budget (and with them every packed
+// image) are the parent's; giving them to the builder is a step of its own.
 constexpr uint32_t trie_lds_bytes(uint32_t image_words, int slices, int waves, uint32_t buf_words) {
     return image_words * 4u + (uint32_t)waves * (64u * (uint32_t)slices * 4u + 2u * buf_words * 4u + 64u);
 }

@@ -31,8 +31,11 @@
 //              document's, or the buffer's padding)
 //   label      the count argmax (first maximum), as score_kernel's
 // A table in the path-sum form (ldgpu_trie.h: one language and a count of at
-// most 4 per root path; trie_kernel<1, maxlen, true>) is counted once per window
-// position instead of once per (position, depth): trie_doc_sum below.
+// most 4 per root path; trie_kernel<1, maxlen, kFormSum>) is counted once per
+// window position instead of once per (position, depth): trie_doc_sum below.
+// Its pair form (Wmax * L <= 63; trie_kernel<1, maxlen, kFormPair>) counts at
+// the payload as it stands -- one counter per (language, W) -- and weighs the
+// counters in the argmax: pair_argmax.
 // Every other document -- shorter than maxg (partial windows), longer than 256
 // bytes, or in a group the staging buffer does not hold -- gets label -1 and
 // is appended to a list (p.left, its length counted in *p.n_left); an indirect
@@ -46,6 +49,9 @@ namespace {
 
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
 typedef __attribute__((address_space(3))) uint8_t lds_u8;
+
+// what the image's entries say (ldgpu_trie.h)
+constexpr int kFormPlain = 0, kFormSum = 1, kFormPair = 2;
 
 __device__ __forceinline__ int64_t rdlane_i64(int64_t v, int l) {
     return (int64_t)((uint64_t)rdlane((uint32_t)v, l) | ((uint64_t)rdlane((uint32_t)((uint64_t)v >> 32), l) << 32));
@@ -93,6 +99,39 @@ __device__ __forceinline__ int count_argmax(const TrieParams& p, uint32_t* cnt, 
     return 255 - (int)(wave_max_u32(best) & 255u);
 }
 
+// The pair form's label: language l's count is the sum over w = 1..wmax of
+// w * cnt[1 + l + L (w - 1)] (consecutive words per w: no bank conflict); from
+// there on count_argmax's key.  Every counter is read and cleared by ONE LDS
+// exchange with 0 (the kernel stands at the LDS array's limit: a read and a
+// write per w cost the array twice) -- all that a document can have touched.
+// p.wmax is wave-uniform: scalar branches.
+__device__ __forceinline__ uint32_t take_count(uint32_t* q) {
+    return __hip_atomic_exchange(q, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ int pair_argmax(const TrieParams& p, uint32_t* cnt, int lane) {
+    uint32_t best = 0;
+    if (lane < p.L) {
+        // (unrolled, shifts and adds: a loop over w, or a product by 3, compiles
+        // to a 64-bit multiply-add)
+        uint32_t* const q = cnt + 1 + lane;
+        const uint32_t wmax = p.wmax, L = (uint32_t)p.L;
+        uint32_t c = take_count(q);
+        if (wmax >= 2) {
+            c += take_count(q + L) << 1;
+            if (wmax >= 3) {
+                const uint32_t c3 = take_count(q + 2 * L);
+                uint32_t c3x2 = c3 << 1;
+                asm("" : "+v"(c3x2));  // (kept apart from c3: the sum would come back as the product)
+                c += c3x2 + c3;
+                if (wmax >= 4) c += take_count(q + 3 * L) << 2;
+            }
+        }
+        const uint32_t k = p.count_sign > 0 ? c : (p.count_sign < 0 ? 0xffffffu - c : 0u);
+        best = (k << 8) | (uint32_t)(255 - lane);
+    }
+    return 255 - (int)(wave_max_u32(best) & 255u);
+}
+
 // a staged label byte as the label: a language 0..253 as it stands, 0xff = -1
 __device__ __forceinline__ int32_t label_of(uint8_t v) { return v == 0xffu ? -1 : (int32_t)v; }
 
@@ -132,6 +171,11 @@ __device__ __forceinline__ void count_depth(const TrieParams& p, uint32_t* cnt, 
     }
 }
 
+// the pair form's count: 1 more at the counter's LDS byte address
+__device__ __forceinline__ void pair_count(uint32_t addr) {
+    __hip_atomic_fetch_add((lds_u32*)(size_t)addr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
 // The path-sum form (ldgpu_trie.h), from the run bytes on: every node's payload
 // says what the whole path to it counts, so a walk is counted once, at the
 // deepest node it reaches inside the document.
@@ -142,11 +186,15 @@ __device__ __forceinline__ void count_depth(const TrieParams& p, uint32_t* cnt, 
 //              entries order by payload, and the payload grows along a path);
 //              payload(m) != 0 and position 4 lane + k inside the document
 //              (cut.in[k]: the depth-1 read is unchecked): one LDS add of the
-//              payload's weight at the payload's counter (language + 1 <= 63)
+//              payload's weight at the payload's counter (language + 1 <= 63);
+//              the pair form: an add of 1 at cnt + payload, the payload being
+//              the byte offset of the pair's counter (cnt_addr: the counters'
+//              LDS byte address, wave-uniform)
 // p.mult is not read: the weights are in the image.
-template <int MAXD>
-__device__ __forceinline__ int trie_doc_sum(const TrieParams& p, uint32_t dead, uint32_t* cnt, const uint32_t (&b)[7],
-                                            const uint32_t (&off)[7], int lane, const TailCut& cut) {
+template <int MAXD, bool PAIR>
+__device__ __forceinline__ int trie_doc_sum(const TrieParams& p, uint32_t dead, uint32_t* cnt, uint32_t cnt_addr,
+                                            const uint32_t (&b)[7], const uint32_t (&off)[7], int lane,
+                                            const TailCut& cut) {
     uint32_t e[4], m[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) m[k] = e[k] = lds_word(off[k]);  // (the direct table at LDS address 0: no check)
@@ -157,6 +205,7 @@ __device__ __forceinline__ int trie_doc_sum(const TrieParams& p, uint32_t dead, 
         // one in eight on text): the other lanes' reads of the dead row took part
         // in the banking for nothing.  The test is three s_or_b64 of the previous
         // step's lane masks.  One branch for the four reads, never one per slot.
+        // (The same branch around the step to depth 3 measured 6 % slower.)
         if (d == 3 && !(live[0] | live[1] | live[2] | live[3])) continue;
         uint32_t n[4];
 #pragma unroll
@@ -173,16 +222,22 @@ __device__ __forceinline__ int trie_doc_sum(const TrieParams& p, uint32_t dead, 
     for (int k = 0; k < 4; ++k) {
         const uint32_t pay = m[k] >> 24;
         const bool in = __builtin_amdgcn_inverse_ballot_w64(cut.in[k]);
-        if (pay != 0 && in)
-            __hip_atomic_fetch_add(&cnt[pay & 63u], (pay >> 6) + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (pay != 0 && in) {
+            if constexpr (PAIR)
+                pair_count(cnt_addr + pay);
+            else
+                __hip_atomic_fetch_add(&cnt[pay & 63u], (pay >> 6) + 1u, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
     }
+    if constexpr (PAIR) return pair_argmax(p, cnt, lane);
     return count_argmax<1, 1>(p, cnt, lane);
 }
 
 // One staged document of maxg..256 bytes at byte `base` of the wave's buffer.
-// SUM: the image has the path-sum form.
-template <int S, int MAXD, bool SUM>
-__device__ __forceinline__ int trie_doc(const TrieParams& p, uint32_t dead, uint32_t* cnt,
+// FORM: what the image's entries say.
+template <int S, int MAXD, int FORM>
+__device__ __forceinline__ int trie_doc(const TrieParams& p, uint32_t dead, uint32_t* cnt, uint32_t cnt_addr,
                                         const uint32_t* buf, uint32_t base, int32_t len, int lane, TailCut& cut) {
     // run bytes 0..6 of the lane's four positions.  Bound: lane 63 reads dwords
     // (base >> 2) + 63 .. + 65, within what score_kernel's lane runs read.
@@ -198,7 +253,12 @@ __device__ __forceinline__ int trie_doc(const TrieParams& p, uint32_t dead, uint
         off[j] = b[j] << 2;
     }
     tail_cut<MAXD>(cut, len, lane);
-    if constexpr (SUM) return trie_doc_sum<MAXD>(p, dead, cnt, b, off, lane, cut);
+    // (run byte 6 serves one walk only, and the compiler would form that walk's
+    // address from the byte with three instructions: its offset as a value,
+    // like the other six)
+    if constexpr (FORM != kFormPlain && MAXD == 4) asm("" : "+v"(off[6]));
+    if constexpr (FORM != kFormPlain)
+        return trie_doc_sum<MAXD, FORM == kFormPair>(p, dead, cnt, cnt_addr, b, off, lane, cut);
     uint32_t e[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) e[k] = lds_word(off[k]);  // (the direct table at LDS address 0: no check)
@@ -225,9 +285,9 @@ __device__ __forceinline__ int trie_doc(const TrieParams& p, uint32_t dead, uint
     return count_argmax<S>(p, cnt, lane);
 }
 
-template <int S, int MAXD, bool SUM>
+template <int S, int MAXD, int FORM>
 __global__ __launch_bounds__(kScoreWaves * 64, kScoreMinWgPerCu * kScoreWaves / 4) void trie_kernel(const TrieParams p) {
-    static_assert(!SUM || S == 1, "the path-sum form has one counter slice");
+    static_assert(FORM == kFormPlain || S == 1, "the path-sum form has one counter slice");
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -242,13 +302,19 @@ __global__ __launch_bounds__(kScoreWaves * 64, kScoreMinWgPerCu * kScoreWaves / 
         uint4* dst = reinterpret_cast<uint4*>(lds);
         for (uint32_t i = tid; i < (p.image_words >> 2); i += blockDim.x) dst[i] = src[i];
     }
-    const uint32_t dead = p.dead;
+    uint32_t dead = p.dead;
+    // (path-sum form: the dead entry kept in a VGPR across the documents -- the
+    // steps' selects would otherwise copy it from its SGPR twice per document)
+    if constexpr (FORM != kFormPlain) asm volatile("" : "+v"(dead));
     __syncthreads();
     uint32_t* const cnt = lds + p.image_words + wave * (64 * S);
+    // (the same counters as an LDS byte address: the dynamic region starts at 0)
+    const uint32_t cnt_addr = 4u * (p.image_words + (uint32_t)wave * (64 * S));
     uint32_t* const buf0 = lds + p.image_words + kScoreWaves * (64 * S) + wave * 2 * kBufWords;
     uint32_t* const buf1 = buf0 + kBufWords;
-    uint8_t* const labels =
-        reinterpret_cast<uint8_t*>(lds + p.image_words + kScoreWaves * (64 * S + 2 * kBufWords)) + wave * 64;
+    // (trie_lds_bytes still counts 64 B per wave behind the buffers, where the
+    // group's labels were staged until they moved into a register: the
+    // footprint, and with it the builder's slot budget, is unchanged)
 #pragma unroll
     for (int s = 0; s < S; ++s) cnt[64 * s + lane] = 0;
     __builtin_amdgcn_wave_barrier();
@@ -268,6 +334,11 @@ __global__ __launch_bounds__(kScoreWaves * 64, kScoreMinWgPerCu * kScoreWaves / 
     bool par = false;
     int64_t prev_g0 = 0;
     int prev_cnt = 0;
+    // The group's labels, document i's in lane i (launch_trie admits 1..63), and
+    // the previous group's until its store: a byte written to LDS per document
+    // and read back per group cost this kernel 1.6 % (it stands at the LDS
+    // array's limit), a compare and a select per document do not.
+    uint32_t labv = 0xffu, prev_labv = 0xffu;
     TailCut cut;
     cut.len = -1;
 
@@ -293,7 +364,7 @@ __global__ __launch_bounds__(kScoreWaves * 64, kScoreMinWgPerCu * kScoreWaves / 
         // the previous group's labels: one coalesced store (0xff = -1)
         {
             const uint32_t l = fresh_lane();
-            if ((int)l < prev_cnt) p.labels[prev_g0 + l] = label_of(labels[l]);
+            if ((int)l < prev_cnt) p.labels[prev_g0 + l] = label_of((uint8_t)prev_labv);
         }
         __builtin_amdgcn_wave_barrier();
         for (int i = 0; i < cntd; ++i) {
@@ -303,63 +374,73 @@ __global__ __launch_bounds__(kScoreWaves * 64, kScoreMinWgPerCu * kScoreWaves / 
             const uint32_t base = blo - (uint32_t)s0;
             int lab;
             if (staged && len >= p.maxg && len <= 256) {
-                lab = trie_doc<S, MAXD, SUM>(p, dead, cnt, cur, base, len, lane, cut);
+                lab = trie_doc<S, MAXD, FORM>(p, dead, cnt, cnt_addr, cur, base, len, lane, cut);
             } else {
                 // left to the indirect launch of score_kernel
                 lab = 0xff;
                 if (lane == 0) p.left[atomicAdd(p.n_left, 1ull)] = g0 + i;
             }
-            if (lane == 0) labels[i] = (uint8_t)lab;
+            labv = lane == i ? (uint32_t)lab : labv;
         }
         __builtin_amdgcn_wave_barrier();
         prev_g0 = g0;
         prev_cnt = cntd;
+        prev_labv = labv;
         offv = offn;
         g0 = g1;
         par = !par;
     }
-    if (lane < prev_cnt) p.labels[prev_g0 + lane] = label_of(labels[lane]);
+    if (lane < prev_cnt) p.labels[prev_g0 + lane] = label_of((uint8_t)prev_labv);
 }
 
-template <int S, int MAXD, bool SUM>
+template <int S, int MAXD, int FORM>
 hipError_t launch_k(const TrieParams& p, int grid, size_t lds, hipStream_t stream) {
-    hipLaunchKernelGGL((trie_kernel<S, MAXD, SUM>), dim3(grid), dim3(kScoreWaves * 64), lds, stream, p);
+    hipLaunchKernelGGL((trie_kernel<S, MAXD, FORM>), dim3(grid), dim3(kScoreWaves * 64), lds, stream, p);
     return hipGetLastError();
 }
-template <int S, bool SUM = false>
+template <int S, int FORM = kFormPlain>
 hipError_t launch_s(const TrieParams& p, int max_len, int grid, size_t lds, hipStream_t stream) {
     switch (max_len) {
-        case 1: return launch_k<S, 1, SUM>(p, grid, lds, stream);
-        case 2: return launch_k<S, 2, SUM>(p, grid, lds, stream);
-        case 3: return launch_k<S, 3, SUM>(p, grid, lds, stream);
-        case 4: return launch_k<S, 4, SUM>(p, grid, lds, stream);
+        case 1: return launch_k<S, 1, FORM>(p, grid, lds, stream);
+        case 2: return launch_k<S, 2, FORM>(p, grid, lds, stream);
+        case 3: return launch_k<S, 3, FORM>(p, grid, lds, stream);
+        case 4: return launch_k<S, 4, FORM>(p, grid, lds, stream);
         default: return hipErrorInvalidValue;
     }
 }
 
-template <int S, int MAXD, bool SUM>
+template <int S, int MAXD, int FORM>
 hipError_t prepare_k(size_t lds, int* blocks) {
-    const void* f = reinterpret_cast<const void*>(&trie_kernel<S, MAXD, SUM>);
+    const void* f = reinterpret_cast<const void*>(&trie_kernel<S, MAXD, FORM>);
     hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, f, kScoreWaves * 64, lds);
 }
-template <int S, bool SUM = false>
+template <int S, int FORM = kFormPlain>
 hipError_t prepare_s(int max_len, size_t lds, int* blocks) {
     switch (max_len) {
-        case 1: return prepare_k<S, 1, SUM>(lds, blocks);
-        case 2: return prepare_k<S, 2, SUM>(lds, blocks);
-        case 3: return prepare_k<S, 3, SUM>(lds, blocks);
-        case 4: return prepare_k<S, 4, SUM>(lds, blocks);
+        case 1: return prepare_k<S, 1, FORM>(lds, blocks);
+        case 2: return prepare_k<S, 2, FORM>(lds, blocks);
+        case 3: return prepare_k<S, 3, FORM>(lds, blocks);
+        case 4: return prepare_k<S, 4, FORM>(lds, blocks);
         default: return hipErrorInvalidValue;
     }
 }
 
 }  // namespace
 
-hipError_t launch_trie(const TrieParams& p, int slices, int max_len, bool sum, int grid, hipStream_t stream) {
+hipError_t launch_trie(const TrieParams& p, int slices, int max_len, bool sum, bool pair, int grid,
+                       hipStream_t stream) {
     const size_t lds = trie_lds_bytes(p.image_words, slices, kScoreWaves, kBufWords);
-    if (sum) return slices == 1 ? launch_s<1, true>(p, max_len, grid, lds, stream) : hipErrorInvalidValue;
+    // lane i <= group holds a group's offsets, lane i < group its labels
+    if (p.group < 1 || p.group > 63) return hipErrorInvalidValue;
+    if (pair) {
+        // the counters pair_argmax reads end at word wmax * L of the wave's 64
+        if (!sum || slices != 1 || p.L < 1 || p.wmax < 1 || p.wmax * (uint32_t)p.L > kTriePairMaxSlot)
+            return hipErrorInvalidValue;
+        return launch_s<1, kFormPair>(p, max_len, grid, lds, stream);
+    }
+    if (sum) return slices == 1 ? launch_s<1, kFormSum>(p, max_len, grid, lds, stream) : hipErrorInvalidValue;
     switch (slices) {
         case 1: return launch_s<1>(p, max_len, grid, lds, stream);
         case 2: return launch_s<2>(p, max_len, grid, lds, stream);
@@ -369,8 +450,10 @@ hipError_t launch_trie(const TrieParams& p, int slices, int max_len, bool sum, i
     }
 }
 
-hipError_t trie_prepare(int slices, int max_len, bool sum, size_t lds_bytes, int* blocks_per_cu) {
-    if (sum) return slices == 1 ? prepare_s<1, true>(max_len, lds_bytes, blocks_per_cu) : hipErrorInvalidValue;
+hipError_t trie_prepare(int slices, int max_len, bool sum, bool pair, size_t lds_bytes, int* blocks_per_cu) {
+    if (pair)
+        return sum && slices == 1 ? prepare_s<1, kFormPair>(max_len, lds_bytes, blocks_per_cu) : hipErrorInvalidValue;
+    if (sum) return slices == 1 ? prepare_s<1, kFormSum>(max_len, lds_bytes, blocks_per_cu) : hipErrorInvalidValue;
     switch (slices) {
         case 1: return prepare_s<1>(max_len, lds_bytes, blocks_per_cu);
         case 2: return prepare_s<2>(max_len, lds_bytes, blocks_per_cu);

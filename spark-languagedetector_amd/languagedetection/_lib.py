@@ -37,7 +37,7 @@ MAX_TOPK = 16  # LDGPU_MAX_TOPK
 LAYOUT_FLAGS = {"lds_bloom": 0x01, "keyed_bloom": 0x02, "keyed_bloom_lines": 0x04, "buckets": 0x08,
                 "wide_keys": 0x10, "direct": 0x20, "packs": 0x40, "lang_blocks": 0x80,
                 "general_keys": 0x100, "keyed_bloom_chunks": 0x200, "classes": 0x400,
-                "narrow_slots": 0x800, "trie": 0x1000, "trie_sum": 0x2000}
+                "narrow_slots": 0x800, "trie": 0x1000, "trie_sum": 0x2000, "trie_pair": 0x4000}
 
 _p = ctypes.c_void_p
 _pp = ctypes.POINTER(ctypes.c_void_p)
