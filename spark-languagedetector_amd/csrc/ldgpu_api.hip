@@ -729,6 +729,7 @@ struct ldgpu_model {
     bool trie_sum = false;  // the image has the path-sum form
     bool trie_pair = false; // ... with the pair payload (one counter per (language, W))
     uint32_t trie_wmax = 0; // path-sum form: the largest W in the image
+    bool trie_doc_pairs = false;  // pair form, L <= 32: the kernel labels two documents per counter pass
     int trie_wg_per_cu = 1;
     // the lists of the documents the trie kernel leaves: stream-ordered scratch
     // from a pool of the model's own that keeps its blocks across synchronises
@@ -1825,6 +1826,10 @@ int model_build(ldgpu_ctx* ctx, int32_t n_langs, const int32_t* gram_lengths, in
         m->trie_sum = trie.sum;
         m->trie_pair = trie.pair;
         m->trie_wmax = trie.wmax;
+        // Two documents per counter pass where both halves of the wave hold
+        // every language: L <= 32.  Diagnostics: LDGPU_NO_TRIE_DOC_PAIRS=1.
+        m->trie_doc_pairs = trie.pair && n_langs <= 32;
+        if (const char* s = diag_env("LDGPU_NO_TRIE_DOC_PAIRS")) m->trie_doc_pairs &= atoi(s) == 0;
     }
     if (e == hipSuccess) e = upload(&m->d_slots, slots, &m->device_bytes);
     if (e == hipSuccess && nw > 0) e = upload(&m->d_wslots, wslots, &m->device_bytes);
@@ -2035,6 +2040,7 @@ int trie_launch(ldgpu_model* m, const ScoreParams& p, hipStream_t st) {
         t.image_words = m->trie_words;
         t.dead = m->trie_dead;
         t.wmax = m->trie_wmax;
+        t.doc_pairs = m->trie_doc_pairs ? 1u : 0u;
         t.L = m->L;
         t.count_sign = m->count_sign;
         t.maxg = p.maxg;

@@ -188,6 +188,7 @@ struct TrieParams {
     uint32_t image_words;       // a multiple of 4
     uint32_t dead;              // the dead entry
     uint32_t wmax;              // the pair form: the largest W in the image (wmax * L <= 63)
+    uint32_t doc_pairs;         // the pair form: 1 = two documents per counter pass (L <= 32), 0 = one
     int32_t L;
     int32_t count_sign;         // sign of the table's one value
     int32_t maxg;               // max(G)

@@ -35,7 +35,9 @@
 // window position instead of once per (position, depth): trie_doc_sum below.
 // Its pair form (Wmax * L <= 63; trie_kernel<1, maxlen, kFormPair>) counts at
 // the payload as it stands -- one counter per (language, W) -- and weighs the
-// counters in the argmax: pair_argmax.
+// counters in the argmax: pair_argmax; with at most 32 languages two documents
+// share a counter pass, one in each half of a counter and of the wave:
+// pair_argmax2.
 // Every other document -- shorter than maxg (partial windows), longer than 256
 // bytes, or in a group the staging buffer does not hold -- gets label -1 and
 // is appended to a list (p.left, its length counted in *p.n_left); an indirect
@@ -132,6 +134,50 @@ __device__ __forceinline__ int pair_argmax(const TrieParams& p, uint32_t* cnt, i
     return 255 - (int)(wave_max_u32(best) & 255u);
 }
 
+// Two documents per counter pass (L <= 32; p.doc_pairs): the first document of
+// a pair counted 1 and the second 0x10000 at the same counters, so a counter's
+// halves hold at most 256 each, and the weighted sum, run ONCE on the packed
+// word, at most 1,024 per half: nothing carries.  Lanes l < L take the counters
+// as pair_argmax does (one exchange per w for BOTH documents); the high half
+// goes to lanes 32 + l by one v_permlane32_swap (lanes 32..63 of its first
+// operand take lanes 0..31 of its second), and each half of the wave finds its
+// document's first maximum with the language lane & 31 in the key: the DPP
+// maximum stops at row_bcast:15, which leaves the halves' maxima in lanes 31
+// and 63.  A first document without a second (the end of a group) is labelled
+// by the same pass: its high halves are 0 and lab[1] is not used.
+struct PairLabels {
+    int lab[2];
+};
+__device__ __forceinline__ PairLabels pair_argmax2(const TrieParams& p, uint32_t* cnt, int lane) {
+    uint32_t c = 0;
+    if (lane < p.L) {
+        uint32_t* const q = cnt + 1 + lane;
+        const uint32_t wmax = p.wmax, L = (uint32_t)p.L;
+        c = take_count(q);
+        if (wmax >= 2) {
+            c += take_count(q + L) << 1;
+            if (wmax >= 3) {
+                const uint32_t c3 = take_count(q + 2 * L);
+                uint32_t c3x2 = c3 << 1;
+                asm("" : "+v"(c3x2));  // (as in pair_argmax)
+                c += c3x2 + c3;
+                if (wmax >= 4) c += take_count(q + 3 * L) << 2;
+            }
+        }
+    }
+    const uint32_t both = __builtin_amdgcn_permlane32_swap(c, c >> 16, false, false)[0];
+    const uint32_t mine = both & 0xffffu;  // lane l: the first document's count of language l, lane 32 + l: the second's
+    const uint32_t l = (uint32_t)lane & 31u;
+    const uint32_t k = p.count_sign > 0 ? mine : (p.count_sign < 0 ? 0xffffffu - mine : 0u);
+    uint32_t v = l < (uint32_t)p.L ? (k << 8) | (255u - l) : 0u;
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false));  // row_shr:1
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false));  // row_shr:2
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false));  // row_shr:4
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false));  // row_shr:8
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false));  // row_bcast:15
+    return PairLabels{{255 - (int)(rdlane(v, 31) & 255u), 255 - (int)(rdlane(v, 63) & 255u)}};
+}
+
 // a staged label byte as the label: a language 0..253 as it stands, 0xff = -1
 __device__ __forceinline__ int32_t label_of(uint8_t v) { return v == 0xffu ? -1 : (int32_t)v; }
 
@@ -171,9 +217,10 @@ __device__ __forceinline__ void count_depth(const TrieParams& p, uint32_t* cnt, 
     }
 }
 
-// the pair form's count: 1 more at the counter's LDS byte address
-__device__ __forceinline__ void pair_count(uint32_t addr) {
-    __hip_atomic_fetch_add((lds_u32*)(size_t)addr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+// the pair form's count: inc (1; the second document of a pair: 0x10000) more
+// at the counter's LDS byte address
+__device__ __forceinline__ void pair_count(uint32_t addr, uint32_t inc) {
+    __hip_atomic_fetch_add((lds_u32*)(size_t)addr, inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
 // The path-sum form (ldgpu_trie.h), from the run bytes on: every node's payload
@@ -187,14 +234,13 @@ __device__ __forceinline__ void pair_count(uint32_t addr) {
 //              payload(m) != 0 and position 4 lane + k inside the document
 //              (cut.in[k]: the depth-1 read is unchecked): one LDS add of the
 //              payload's weight at the payload's counter (language + 1 <= 63);
-//              the pair form: an add of 1 at cnt + payload, the payload being
+//              the pair form: an add of inc at cnt + payload, the payload being
 //              the byte offset of the pair's counter (cnt_addr: the counters'
 //              LDS byte address, wave-uniform)
-// p.mult is not read: the weights are in the image.
+// p.mult is not read: the weights are in the image.  The label is the caller's.
 template <int MAXD, bool PAIR>
-__device__ __forceinline__ int trie_doc_sum(const TrieParams& p, uint32_t dead, uint32_t* cnt, uint32_t cnt_addr,
-                                            const uint32_t (&b)[7], const uint32_t (&off)[7], int lane,
-                                            const TailCut& cut) {
+__device__ __forceinline__ void trie_doc_sum(uint32_t dead, uint32_t* cnt, uint32_t cnt_addr, const uint32_t (&b)[7],
+                                             const uint32_t (&off)[7], const TailCut& cut, uint32_t inc) {
     uint32_t e[4], m[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) m[k] = e[k] = lds_word(off[k]);  // (the direct table at LDS address 0: no check)
@@ -205,7 +251,9 @@ __device__ __forceinline__ int trie_doc_sum(const TrieParams& p, uint32_t dead, 
         // one in eight on text): the other lanes' reads of the dead row took part
         // in the banking for nothing.  The test is three s_or_b64 of the previous
         // step's lane masks.  One branch for the four reads, never one per slot.
-        // (The same branch around the step to depth 3 measured 6 % slower.)
+        // (The same branch around the step to depth 3 measured 6 % slower; every
+        // read from depth 3 on under its slot's own live lane mask, 1.7 % slower
+        // in six alternating runs: DESIGN.md.)
         if (d == 3 && !(live[0] | live[1] | live[2] | live[3])) continue;
         uint32_t n[4];
 #pragma unroll
@@ -224,21 +272,22 @@ __device__ __forceinline__ int trie_doc_sum(const TrieParams& p, uint32_t dead, 
         const bool in = __builtin_amdgcn_inverse_ballot_w64(cut.in[k]);
         if (pay != 0 && in) {
             if constexpr (PAIR)
-                pair_count(cnt_addr + pay);
+                pair_count(cnt_addr + pay, inc);
             else
                 __hip_atomic_fetch_add(&cnt[pay & 63u], (pay >> 6) + 1u, __ATOMIC_RELAXED,
                                        __HIP_MEMORY_SCOPE_WORKGROUP);
         }
     }
-    if constexpr (PAIR) return pair_argmax(p, cnt, lane);
-    return count_argmax<1, 1>(p, cnt, lane);
 }
 
 // One staged document of maxg..256 bytes at byte `base` of the wave's buffer.
-// FORM: what the image's entries say.
+// FORM: what the image's entries say.  Returns the document's label; the pair
+// form only counts (inc at each counter) and returns 0: the label is the
+// document loop's, once per document or once per two (trie_kernel).
 template <int S, int MAXD, int FORM>
 __device__ __forceinline__ int trie_doc(const TrieParams& p, uint32_t dead, uint32_t* cnt, uint32_t cnt_addr,
-                                        const uint32_t* buf, uint32_t base, int32_t len, int lane, TailCut& cut) {
+                                        const uint32_t* buf, uint32_t base, int32_t len, int lane, TailCut& cut,
+                                        uint32_t inc) {
     // run bytes 0..6 of the lane's four positions.  Bound: lane 63 reads dwords
     // (base >> 2) + 63 .. + 65, within what score_kernel's lane runs read.
     const uint32_t sh = base & 3u;  // wave-uniform
@@ -257,8 +306,11 @@ __device__ __forceinline__ int trie_doc(const TrieParams& p, uint32_t dead, uint
     // address from the byte with three instructions: its offset as a value,
     // like the other six)
     if constexpr (FORM != kFormPlain && MAXD == 4) asm("" : "+v"(off[6]));
-    if constexpr (FORM != kFormPlain)
-        return trie_doc_sum<MAXD, FORM == kFormPair>(p, dead, cnt, cnt_addr, b, off, lane, cut);
+    if constexpr (FORM != kFormPlain) {
+        trie_doc_sum<MAXD, FORM == kFormPair>(dead, cnt, cnt_addr, b, off, cut, inc);
+        if constexpr (FORM == kFormPair) return 0;
+        return count_argmax<1, 1>(p, cnt, lane);
+    }
     uint32_t e[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) e[k] = lds_word(off[k]);  // (the direct table at LDS address 0: no check)
@@ -270,12 +322,12 @@ __device__ __forceinline__ int trie_doc(const TrieParams& p, uint32_t dead, uint
 #pragma unroll
             for (int k = 0; k < 4; ++k) n[k] = lds_word((e[k] >> 16) + off[k + d]);
         }
-        const uint32_t inc = p.mult[d];
-        if (inc) {
-            if (d == 1) count_depth<1>(p, cnt, e, cut, inc);
-            if (d == 2) count_depth<2>(p, cnt, e, cut, inc);
-            if (d == 3) count_depth<3>(p, cnt, e, cut, inc);
-            if (d == 4) count_depth<4>(p, cnt, e, cut, inc);
+        const uint32_t mul = p.mult[d];
+        if (mul) {
+            if (d == 1) count_depth<1>(p, cnt, e, cut, mul);
+            if (d == 2) count_depth<2>(p, cnt, e, cut, mul);
+            if (d == 3) count_depth<3>(p, cnt, e, cut, mul);
+            if (d == 4) count_depth<4>(p, cnt, e, cut, mul);
         }
         if (d < MAXD) {
 #pragma unroll
@@ -367,20 +419,50 @@ __global__ __launch_bounds__(kScoreWaves * 64, kScoreMinWgPerCu * kScoreWaves / 
             if ((int)l < prev_cnt) p.labels[prev_g0 + l] = label_of((uint8_t)prev_labv);
         }
         __builtin_amdgcn_wave_barrier();
+        // The pair form with p.doc_pairs: the documents the kernel scores are
+        // labelled two at a time.  The first of a pair counts 1 and waits (pend:
+        // its index in the group, -1: none), the second counts 0x10000 at the
+        // same counters, and one pass labels both (pair_argmax2).  A document
+        // left to score_kernel touches no counter and does not break a pair; a
+        // first document still pending at the end of the group is labelled
+        // alone, so the group's label store is what it was.
+        int pend = -1;
         for (int i = 0; i < cntd; ++i) {
             // 32-bit geometry (a staged group: b - s0 and len lie in [0, kBufBytes])
             const uint32_t blo = rdlane((uint32_t)offv, i);
             const int32_t len = (int32_t)(rdlane((uint32_t)offv, i + 1) - blo);
             const uint32_t base = blo - (uint32_t)s0;
-            int lab;
             if (staged && len >= p.maxg && len <= 256) {
-                lab = trie_doc<S, MAXD, FORM>(p, dead, cnt, cnt_addr, cur, base, len, lane, cut);
+                if constexpr (FORM == kFormPair) {
+                    const int first = __builtin_amdgcn_readfirstlane(pend);  // (wave-uniform: kept scalar)
+                    const uint32_t inc = first < 0 ? 1u : 0x10000u;
+                    trie_doc<S, MAXD, FORM>(p, dead, cnt, cnt_addr, cur, base, len, lane, cut, inc);
+                    if (!p.doc_pairs) {
+                        const int lab = pair_argmax(p, cnt, lane);
+                        labv = lane == i ? (uint32_t)lab : labv;
+                    } else if (first < 0) {
+                        pend = i;
+                    } else {
+                        const PairLabels two = pair_argmax2(p, cnt, lane);
+                        labv = lane == first ? (uint32_t)two.lab[0] : labv;
+                        labv = lane == i ? (uint32_t)two.lab[1] : labv;
+                        pend = -1;
+                    }
+                } else {
+                    const int lab = trie_doc<S, MAXD, FORM>(p, dead, cnt, cnt_addr, cur, base, len, lane, cut, 1u);
+                    labv = lane == i ? (uint32_t)lab : labv;
+                }
             } else {
                 // left to the indirect launch of score_kernel
-                lab = 0xff;
                 if (lane == 0) p.left[atomicAdd(p.n_left, 1ull)] = g0 + i;
+                labv = lane == i ? 0xffu : labv;
             }
-            labv = lane == i ? (uint32_t)lab : labv;
+        }
+        if constexpr (FORM == kFormPair) {
+            if (pend >= 0) {
+                const PairLabels two = pair_argmax2(p, cnt, lane);
+                labv = lane == pend ? (uint32_t)two.lab[0] : labv;
+            }
         }
         __builtin_amdgcn_wave_barrier();
         prev_g0 = g0;
